@@ -5,7 +5,13 @@ One step = one pass of the transform (xsk_gpu_echo_dev: parse + full-payload che
 rewrite + records + stats counters) over one batch of frames already resident in HBM.  Each step
 gets a fresh, never-transformed batch (a pool of pre-generated batches), so no step sees replies.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|p98] [--no-cpu] [--host-inclusive]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5|p98] [--dump-outputs DIR]
+                  [--full [--no-cpu] [--no-rx-loop] [--host-inclusive] [--no-host-multi]]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints
+the result line.  Everything else lives behind --full: the check of every step's outputs (`verified`), the
+read-only streaming ceiling of the roofline, the CPU baseline, the RX-loop leg (tools/rxring) and the
+PCIe-inclusive legs (--host-inclusive at N = 1, host_inclusive_multi at N > 1).
 
 Multi-GPU: one process per GPU.  Run as `python bench.py --gpus N` (no launcher) the script starts
 `torch.distributed.run --nproc-per-node N` itself as a child process before anything touches a GPU, and
@@ -417,17 +423,82 @@ def pool_plan(n, stride, free, warmup, steps, cap=0):
     return pool, pool < warmup + steps
 
 
+DUMP_FRAMES = 1 << 18  # frames whose descriptor, verdict and record are dumped (all of them when the batch is smaller)
+DUMP_UMEM_FRAMES = 4096  # of those, the frames whose bytes are dumped
+DUMP_UMEM_BYTES = 1536  # leading bytes of each (the whole stride when it is shorter)
+
+
+def dump_sample(n, m=DUMP_FRAMES, seed=0x0D0E):
+    """The frames --dump-outputs writes: all of a batch of at most `m` frames, else one frame from each of m equal
+    strata, its place in the stratum drawn from a fixed seed (ascending, distinct, the same in every run)."""
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    lo = np.arange(m, dtype=np.int64) * n // m
+    hi = (np.arange(m, dtype=np.int64) + 1) * n // m
+    return lo + np.random.default_rng(seed).integers(0, hi - lo)
+
+
+def dump_outputs(path, umem, descs, verd, recs, stats, n, stride):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as float32 / float64 .npy
+    files (about 46 MB at 1 M frames).  The descriptors, verdicts and records of a fixed sample of the batch
+    (dump_sample) and the rewritten bytes of 4096 of those frames (bytes past a frame's length are not the transform's
+    and read as 0); over the whole batch the count of each verdict and the sum of each record field; and the stats
+    counters (which accumulate over every step since the start, warm-up included)."""
+    import xsknet_amd as X
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample(n)
+    d_idx = torch.from_numpy(idx).to(umem.device)
+    ds = descs.view(-1, 16)[d_idx].cpu().numpy().view(X.DESC_DTYPE).reshape(-1)
+    rs = recs.view(-1, 16)[d_idx].cpu().numpy().view(X.REC_DTYPE).reshape(-1)
+    sub = np.arange(0, len(idx), max(1, len(idx) // DUMP_UMEM_FRAMES))[:DUMP_UMEM_FRAMES]
+    width = min(stride, DUMP_UMEM_BYTES)
+    addr = torch.from_numpy(ds["addr"][sub].astype(np.int64)).to(umem.device)
+    offs = addr[:, None] + torch.arange(width, dtype=torch.int64, device=umem.device)[None, :]
+    assert int(offs.max().item()) < umem.numel()
+    frames = umem[offs].cpu().numpy().astype(np.float32)
+    frames[np.arange(width)[None, :] >= ds["len"][sub][:, None]] = 0
+    # column sums of the 16 record bytes, folded into the little-endian fields
+    cols = recs.view(-1, 16)[:n].sum(0, dtype=torch.int64).cpu().numpy()
+    at = {k: X.REC_DTYPE.fields[k][1] for k in X.REC_DTYPE.names}
+    rec_sums = [float(sum(int(cols[at[k] + i]) << (8 * i) for i in range(X.REC_DTYPE[k].itemsize)))
+                for k in X.REC_DTYPE.names]
+    st = stats.cpu().numpy().view(X.STATS_DTYPE)[0]
+    arrays = {
+        "sample_index": idx.astype(np.float64),
+        "descs": np.stack([ds[k].astype(np.float64) for k in X.DESC_DTYPE.names], axis=1),
+        "verdicts": verd[d_idx].cpu().numpy().astype(np.float32),
+        "records": np.stack([rs[k].astype(np.float32) for k in X.REC_DTYPE.names], axis=1),
+        "frames_index": idx[sub].astype(np.float64),
+        "frames": frames,
+        "verdict_counts": torch.bincount(verd[:n].to(torch.int32), minlength=256).cpu().numpy().astype(np.float64),
+        "record_sums": np.array(rec_sums, np.float64),
+        "stats": np.array([float(st[k]) for k in X.STATS_DTYPE.names if k != "timestamp"], np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--host-inclusive", action="store_true", help="also measure the PCIe-inclusive rate")
-    ap.add_argument("--no-rx-loop", action="store_true", help="skip the RX-loop leg (tools/rxring, N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check every step's outputs, measure the read ceiling of the "
+                         "roofline, the CPU baseline and the RX loop (N = 1) or the multi-GPU host-inclusive leg "
+                         "(N > 1); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (a fixed sample of the rewritten "
+                         "frames, descriptors, verdicts and records, and the counters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--host-inclusive", action="store_true",
+                    help="--full: also measure the PCIe-inclusive rate")
+    ap.add_argument("--no-rx-loop", action="store_true",
+                    help="--full: skip the RX-loop leg (tools/rxring, N = 1 only)")
     ap.add_argument("--no-host-multi", action="store_true",
-                    help="N > 1: skip rank 0's multi-GPU host-inclusive leg after the timed region")
+                    help="--full, N > 1: skip rank 0's multi-GPU host-inclusive leg after the timed region")
     ap.add_argument("--pool-cap", type=int, default=0, help="cap the batch pool (rehearsals on a shared GPU)")
     ap.add_argument("--alloc", default="slab", choices=("slab", "separate"),
                     help="batch pool as one device allocation (slab, like one UMEM region) or one per batch")
@@ -440,6 +511,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.host_inclusive and not args.full:
+        raise SystemExit("--host-inclusive is a leg of --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the parent never touches a GPU library: it counts GPUs in the KFD topology and spawns the ranks
         ngpu = None if SHARE_GPU else kfd_gpu_count()
@@ -549,28 +622,40 @@ def main():
         kern_ms, launches = ev_ms, K
         timer_src = "HIP events on the launch stream around the K back-to-back launches (one launch per step)"
 
-    # ---- correctness of what was timed: every frame of every step accepted and counted, every step's verdicts
-    # TX_REPLY and records carrying both verified input checksums (checked on the device after the timed region) ----
-    st = stats.cpu().numpy().view(X.STATS_DTYPE)[0]
-    ok = args.variant >= 0 or (int(st["rx_packets"]) == (W + K) * n and int(st["tx_packets"]) == (W + K) * n)
-    ok = ok and all(bool((v == 0).all().item()) for v in verds)
-    ok = ok and all(bool((r.view(-1, 16)[:, 1] == 3).all().item()) for r in recss)  # xsk_gpu_rec.flags
-    checked = {"steps_with_outputs_checked": (W + K) if per_step else pool,
-               "verdicts": "every step" if per_step else "the last use of each pooled batch",
-               "records": "every step" if per_step else "the last step",
-               "counters": "every step (rx / tx packets == steps x frames)"}
+    # ---- --dump-outputs: the last timed step's outputs, before anything else touches them (rank 0's) ----
+    if args.dump_outputs and rank == 0:
+        s = W + K - 1
+        nbytes = dump_outputs(args.dump_outputs, umems[s % pool], descss[s % pool], verds[s if per_step else s % pool],
+                              recss[s if per_step else 0], stats, n, stride)
+        log(f"[rank 0] wrote the last step's outputs to {args.dump_outputs} ({nbytes / 2**20:.1f} MiB)")
 
-    # read-only streaming ceiling over one batch slab (context for the roofline)
-    out = torch.zeros(1, dtype=torch.int64, device=dev)
-    X.stream_read_dev(umems[0], batch_bytes, out, stream)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(5):
+    if args.full:
+        # ---- correctness of what was timed: every frame of every step accepted and counted, every step's verdicts
+        # TX_REPLY and records carrying both verified input checksums (checked on the device after the timed
+        # region) ----
+        st = stats.cpu().numpy().view(X.STATS_DTYPE)[0]
+        ok = args.variant >= 0 or (int(st["rx_packets"]) == (W + K) * n and int(st["tx_packets"]) == (W + K) * n)
+        ok = ok and all(bool((v == 0).all().item()) for v in verds)
+        ok = ok and all(bool((r.view(-1, 16)[:, 1] == 3).all().item()) for r in recss)  # xsk_gpu_rec.flags
+        checked = {"steps_with_outputs_checked": (W + K) if per_step else pool,
+                   "verdicts": "every step" if per_step else "the last use of each pooled batch",
+                   "records": "every step" if per_step else "the last step",
+                   "counters": "every step (rx / tx packets == steps x frames)"}
+
+        # read-only streaming ceiling over one batch slab (context for the roofline)
+        out = torch.zeros(1, dtype=torch.int64, device=dev)
         X.stream_read_dev(umems[0], batch_bytes, out, stream)
-    e1.record(stream)
-    torch.cuda.synchronize()
-    read_ceiling = batch_bytes * 5 / (e0.elapsed_time(e1) / 1e3) / 1e9
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(5):
+            X.stream_read_dev(umems[0], batch_bytes, out, stream)
+        e1.record(stream)
+        torch.cuda.synchronize()
+        read_ceiling = batch_bytes * 5 / (e0.elapsed_time(e1) / 1e3) / 1e9
+    else:  # a plain run times the steps and nothing else
+        ok, read_ceiling = True, None
+        checked = "not checked: a plain run only times the steps (--full checks every step's outputs)"
 
     kern_avg_ms = kern_ms / max(launches, 1)
     agg = reduce_ranks(rank, world, local, wall=wall, ev_ms=ev_ms, ok=ok, frames=K * n, frame_bytes=K * frame_bytes,
@@ -603,7 +688,7 @@ def main():
                        "frame_bytes_per_gpu_step": frame_bytes, "parallelism": f"shard{world}:round-robin",
                        "layout": "device-resident UMEM slab + xdp_desc array", "pool_alloc": args.alloc,
                        "rearm_in_timed_region": rearm_in_loop},
-            "verified": bool(ok_all == world),
+            "verified": bool(ok_all == world) if args.full else None,
             "verification": checked,
             **({"ab_variant": args.variant, "note": "A/B timing of a tuning variant, not the shipped kernel"}
                if args.variant >= 0 else {}),
@@ -612,7 +697,7 @@ def main():
                          "traffic_source": traffic_src, "build_id": X.build_id(),
                          "kernel": kernel, "kernel_avg_us": round(kern_avg_ms * 1e3, 2), "kernel_timer": timer_src,
                          "algorithmic_bytes_per_launch": frame_bytes,
-                         "read_ceiling_gbs": round(read_ceiling, 1),
+                         "read_ceiling_gbs": round(read_ceiling, 1) if read_ceiling else None,
                          # context for frac: a plain 16-B read of the same slab on this GPU (xsk_gpu_stream_read_dev);
                          # read kernels reach 0.90 of spec only as an asymptote of multi-GiB slabs
                          "frac_of_read_ceiling": frac_of_ceiling(achieved, read_ceiling),
@@ -620,20 +705,20 @@ def main():
             "per_rank": per_rank,
             "event_ms_per_step": round(ev_max / K, 4),
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             log("[rank 0] CPU baseline ...")
             res["cpu_baseline"] = cpu_baseline(args.config)
-        if world == 1 and not args.no_rx_loop:
+        if args.full and world == 1 and not args.no_rx_loop:
             log("[rank 0] RX loop (tools/rxring) ...")
             res["rx_loop"] = rx_loop()
-        if args.host_inclusive and world == 1:
+        if args.full and args.host_inclusive and world == 1:
             log("[rank 0] host-inclusive ...")
             res["host_inclusive"] = host_inclusive(args.config, local)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()  # the other ranks leave here: their GPUs are free for rank 0's multi leg
     if rank == 0:
-        if world > 1 and not args.no_host_multi:
+        if args.full and world > 1 and not args.no_host_multi:
             log(f"[rank 0] host-inclusive over {world} GPUs ...")
             del slab, umems, descss  # the batch pool: HBM for the STAGED mirrors
             torch.cuda.empty_cache()

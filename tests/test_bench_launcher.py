@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.conftest import ROOT
@@ -275,3 +276,31 @@ def test_rx_loop_leg_parses_rxring_and_never_fails_the_line(tmp_path, monkeypatc
     assert r["step64_pipe4"]["mframes_per_s"] == 28.7
     assert "error" in r["step1024"]
     assert r["step64_pipe8_hwq8"]["env"] == {"GPU_MAX_HW_QUEUES": "8"}
+
+
+def test_host_inclusive_is_a_leg_of_full(monkeypatch):
+    """The PCIe-inclusive leg runs only under --full; asking for it in a plain run is refused, not ignored."""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--host-inclusive"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert "--full" in str(e.value)
+
+
+def test_dump_sample_is_fixed_ascending_and_covers_the_batch():
+    """--dump-outputs' frame sample: every frame of a small batch; of a large one, one frame per stratum, ascending and
+    distinct, identical from call to call (the dumps of two builds are compared output for output)."""
+    bench = _bench()
+    assert bench.dump_sample(1000).tolist() == list(range(1000))
+    assert bench.dump_sample(bench.DUMP_FRAMES).tolist() == list(range(bench.DUMP_FRAMES))
+    for n in (bench.DUMP_FRAMES + 1, 300001, 1 << 20, (1 << 26) + 5):
+        idx = bench.dump_sample(n)
+        assert idx.dtype == np.int64 and len(idx) == bench.DUMP_FRAMES
+        assert idx[0] >= 0 and idx[-1] < n and (np.diff(idx) > 0).all()
+        m = np.arange(bench.DUMP_FRAMES, dtype=np.int64)
+        assert (idx >= m * n // bench.DUMP_FRAMES).all() and (idx < (m + 1) * n // bench.DUMP_FRAMES).all()
+        assert (idx == bench.dump_sample(n)).all()
+    # the dump of a 1 M-frame batch stays under the 64 MB bound: 8 B index + 24 B descriptor + 4 B verdict + 44 B record
+    # per sampled frame, 8 B index + 4 B per dumped byte per frame with bytes, 256 + 11 + 4 float64 totals
+    total = bench.DUMP_FRAMES * (8 + 24 + 4 + 44) + bench.DUMP_UMEM_FRAMES * (8 + 4 * bench.DUMP_UMEM_BYTES) + 8 * 271
+    assert total + 9 * 128 <= 64 * 10**6

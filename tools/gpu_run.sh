@@ -7,7 +7,7 @@
 #   tests               the whole -m gpu suite, in collection order, once
 #   tests:<path>        one test file or node id
 #   smoke               __graft_entry__.smoke()
-#   bench:<config>      bench.py --config <config> --steps 20 --warmup 5 --no-cpu
+#   bench:<config>      bench.py --full --config <config> --steps 20 --warmup 5 --no-cpu
 #   hostlat             tools/hostlat.py, LOWLAT / ZEROCOPY, 64 and 1024 frames of 64 and 1500 B (C1 shape)
 #   rxring              tools/rxring, plain and depth-4 pipelined RX loop at 64- and 1024-frame steps, every reply
 #                       checked and every failure attributed (tools/rxring.c)
@@ -33,7 +33,7 @@ for s in "$@"; do
     tests) run tests 900 $PYT tests -m gpu || exit 1 ;;
     tests:*) run "tests_$(echo ${s#tests:} | sed 's/.*:://; s/.*\///; s/\.py$//' | tr -c 'a-zA-Z0-9_\n' _)" 600 $PYT "${s#tests:}" -m gpu || exit 1 ;;
     smoke) run smoke 120 python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    bench:*) run "bench_${s#bench:}" 300 python bench.py --config ${s#bench:} --steps 20 --warmup 5 --no-cpu || exit 1 ;;
+    bench:*) run "bench_${s#bench:}" 300 python bench.py --full --config ${s#bench:} --steps 20 --warmup 5 --no-cpu || exit 1 ;;
     hostlat) run hostlat 400 python tools/hostlat.py --lens 64,1500 --modes lowlat,zerocopy --batches 64,1024 --reps 300 || exit 1 ;;
     rxring) run rxring 400 python tools/rxring_runs.py || exit 1 ;;
     rxdiag) run rxdiag 400 python tools/rxring_runs.py --diag || exit 1 ;;

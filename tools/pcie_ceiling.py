@@ -1,6 +1,6 @@
 """PCIe ceilings behind the host-inclusive rate: what the copy engines move between a pinned host
 UMEM and the device at the bench's host-inclusive shape (262 144 frames of 1500 B at a 4 KiB stride), next to
-`bench.py --host-inclusive`'s staged rate.
+`bench.py --full --host-inclusive`'s staged rate.
 
     python tools/pcie_ceiling.py [--frames 262144] [--len 1500] [--stride 4096] [--reps 5]
 
