@@ -26,7 +26,10 @@
  *     rewrites), and only reads bytes inside [align16(addr), align16(addr) + 64) u [addr, addr + len);
  *   - a 16-B aligned reply whose [addr, addr + 64) lies in the UMEM is stored as that whole 64-byte
  *     window (bytes 38-63 are written back with the values they held), so HBM sees full sectors
- *     instead of read-modify-write partial ones; unaligned replies are stored byte-exact.
+ *     instead of read-modify-write partial ones; unaligned replies are stored byte-exact;
+ *   - an ICMPv6 reply (wire mode with XSK_GPU_OPT_IPV6) changes only bytes [0, 12), [l3 + 8, l3 + 40), l4 and
+ *     [l4 + 2, l4 + 4), l4 = l3 + 40, all below l4 + 4 <= 66 <= len; an aligned one leaves as the whole 64-byte
+ *     window only when l4 + 4 <= 64 (no tag or one), any other byte-exact.
  */
 #ifndef XSK_GPU_H
 #define XSK_GPU_H
@@ -93,6 +96,7 @@ enum xsk_gpu_verdict {
 #define XSK_GPU_F_ICMP_CSUM_OK 0x02u /* len >= 42 and the ICMP message [34,len) sums to 0xFFFF */
 #define XSK_GPU_F_VLAN 0x04u         /* wire mode: one or two VLAN tags were skipped           */
 #define XSK_GPU_F_IP_OPTIONS 0x08u   /* wire mode: IHL > 5 (IPv4 options present)             */
+#define XSK_GPU_F_IPV6 0x10u         /* wire mode, XSK_GPU_OPT_IPV6: the frame was parsed as IPv6 */
 
 /* ------------------------------------------------------------------------------------------ */
 /* Wire-format widening (build-added).  opts == 0 is the reference's gates */
@@ -124,7 +128,43 @@ enum xsk_gpu_verdict {
 #define XSK_GPU_OPT_STRICT_IPV4 0x1u
 #define XSK_GPU_OPT_VLAN 0x2u
 #define XSK_GPU_OPT_VERIFY_CSUM 0x4u
-#define XSK_GPU_OPT_ALL 0x7u
+#define XSK_GPU_OPT_ALL 0x7u  /* every IPv4 option */
+
+/* ------------------------------------------------------------------------------------------ */
+/* ICMPv6 echo (build-added; RFC 4443 §4.1-4.2, RFC 8200).  XSK_GPU_OPT_IPV6 selects wire mode  */
+/* and also answers ICMPv6 echo requests; without it an inner ethertype of 0x86DD stays         */
+/* DROP_NOT_IPV4.  Everything up to the inner ethertype is as above (len < 14, tags only with   */
+/* XSK_GPU_OPT_VLAN); 0x0800 follows the IPv4 path above bit for bit; 0x86DD, with l3 as after  */
+/* the tags and l4 = l3 + 40:                                                                   */
+/*   DROP_SHORT if len < l3 + 40;                                                               */
+/*   with XSK_GPU_OPT_STRICT_IPV4 ("strict IP" for this family): DROP_BAD_IP unless the version */
+/*        (byte l3 >> 4) is 6, the payload length plen = be16(l3 + 4) satisfies plen >= 8 and   */
+/*        l4 + plen <= len (plen == 0, a jumbogram, is bad), and neither the source (byte       */
+/*        l3 + 8) nor the destination (byte l3 + 24) is multicast (0xFF: the swap would make a  */
+/*        multicast source); the message is [l4, l4 + plen) (Ethernet padding excluded),        */
+/*        without STRICT [l4, len);                                                             */
+/*   DROP_NOT_ICMP unless the next header (byte l3 + 6) is 58: extension headers are not walked;*/
+/*   DROP_SHORT if len < l4 + 8;                                                                */
+/*   DROP_NOT_ECHO unless type (byte l4) == 128 (and, STRICT, code == 0);                       */
+/*   with XSK_GPU_OPT_VERIFY_CSUM: DROP_BAD_CSUM unless icmp_sum == 0xFFFF (IPv6 has no header  */
+/*        checksum);                                                                            */
+/*   otherwise TX_REPLY: MACs swapped, the 16-byte addresses at l3 + 8 / l3 + 24 swapped, type  */
+/*        = 129, checksum at l4 + 2 updated by csum_replace2(128 -> 129) in the reference's u16 */
+/*        arithmetic on the little-endian-loaded field (xsk_receive.c:101-111).                 */
+/* Records of IPv6 frames: verdict always; every other field only for TX_REPLY, DROP_NOT_ECHO   */
+/* and DROP_BAD_CSUM, else zero: eth_proto = 0x86DD, ip_vihl = byte l3, ip_proto = 58, icmp_*   */
+/* from l4; ip_sum = the folded sum of the RFC 8200 §8.1 pseudo-header (source, destination,    */
+/* the message length as a 32-bit value, three zero bytes, 58); icmp_sum = the folded sum of    */
+/* that pseudo-header followed by the message (odd tail zero-padded).  Flags: F_IPV6 always,    */
+/* F_ICMP_CSUM_OK iff icmp_sum == 0xFFFF, F_VLAN as above; never F_IP_CSUM_OK / F_IP_OPTIONS.   */
+/* Limitations: XSK_GPU_OPT_MASK is every valid bit; 0x8 is reserved and rejected (-EINVAL).    */
+/* The resident XSK_GPU_MODE_LOWLAT kernel has no IPv6 instance: a LOWLAT context with          */
+/* XSK_GPU_OPT_IPV6 set serves every batch through the launch path (same results, a launch per  */
+/* batch; xsk_gpu_ctx_mode() still reports LOWLAT).  xsk_gpu_classify_dev still passes 0x86DD   */
+/* to the kernel stack.                                                                         */
+/* ------------------------------------------------------------------------------------------ */
+#define XSK_GPU_OPT_IPV6 0x10u /* wire mode also answers ICMPv6 echo requests */
+#define XSK_GPU_OPT_MASK 0x17u /* every valid bit; 0x8 is reserved and rejected */
 
 /* Optional 16-byte per-frame result record. Parsed fields are those the reference reads
  * (xsk_receive.c:135,140,144,157); they are all zero when len < 20 because the reference reads

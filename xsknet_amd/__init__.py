@@ -26,7 +26,7 @@ __all__ = [
     "MODE_ZEROCOPY", "MODE_STAGED", "MODE_LOWLAT", "LOWLAT_MAX", "MultiContext", "tune_lib", "lowlat_reserve", "lowlat_cap", "timing_enable", "timing_read", "Ring", "FramePool", "RxResult",
     "classify_dev", "XDP_DROP", "XDP_PASS", "XDP_REDIRECT", "DROP_BAD_IP", "DROP_BAD_CSUM",
     "OPT_STRICT_IPV4", "OPT_VLAN", "OPT_VERIFY_CSUM", "OPT_ALL", "F_IP_CSUM_OK", "F_ICMP_CSUM_OK", "F_VLAN",
-    "F_IP_OPTIONS",
+    "F_IP_OPTIONS", "OPT_IPV6", "OPT_MASK", "F_IPV6",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -40,7 +40,8 @@ VERDICTS = ["TX_REPLY", "DROP_SHORT", "DROP_NOT_IPV4", "DROP_NOT_ICMP", "DROP_NO
             "DROP_BAD_IP", "DROP_BAD_CSUM"]
 # wire-format options (include/xsk_gpu.h XSK_GPU_OPT_*) and record flags
 OPT_STRICT_IPV4, OPT_VLAN, OPT_VERIFY_CSUM, OPT_ALL = 1, 2, 4, 7
-F_IP_CSUM_OK, F_ICMP_CSUM_OK, F_VLAN, F_IP_OPTIONS = 1, 2, 4, 8
+OPT_IPV6, OPT_MASK = 0x10, 0x17  # ICMPv6 echo too; every valid bit (0x8 is reserved)
+F_IP_CSUM_OK, F_ICMP_CSUM_OK, F_VLAN, F_IP_OPTIONS, F_IPV6 = 1, 2, 4, 8, 0x10
 MODE_ZEROCOPY, MODE_STAGED, MODE_LOWLAT = 0, 1, 2
 LOWLAT_MAX = 1024  # XSK_GPU_LOWLAT_MAX
 RX_PIPE_MAX = 8  # XSK_GPU_RX_PIPE_MAX

@@ -120,7 +120,8 @@ __global__ __launch_bounds__(256) void synth_kernel(SynthArgs a) {
 
 // Staged host mode: gather the rewritten header bytes of every TX_REPLY frame into a packed [n][96]
 // array so the host can scatter them back into its UMEM (never touching unowned bytes): bytes [0, 38)
-// in reference mode, [0, min(len, 96)) in wire mode (its rewrite ends at l4 + 4 <= 86 <= len).
+// in reference mode, [0, min(len, 96)) in wire mode (its rewrite ends at l4 + 4 <= len: at most 86 for
+// IPv4 behind two tags and 40 option bytes, 66 for IPv6 behind two tags).
 constexpr uint32_t kPack = 96;
 __global__ __launch_bounds__(256) void pack_headers_kernel(const uint8_t* umem, const xsk_gpu_desc* descs,
                                                            const uint8_t* verdicts, uint32_t n, uint8_t* pack,

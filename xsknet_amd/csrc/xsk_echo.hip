@@ -138,7 +138,7 @@ uint32_t xsk_gpu__num_cu(int device) {
     return (uint32_t)v;
 }
 
-// One transform launch (reference mode for opts == 0, wire mode otherwise).  Counters: device memory
+// One transform launch (reference mode for opts == 0, wire mode otherwise, its dual-stack kernel with XSK_GPU_OPT_IPV6).  Counters: device memory
 // (hoststats == 0) -> every workgroup adds its four counters with device-scope atomics, one launch;
 // mapped host memory (hoststats == 1, the zerocopy host context: d_stats is a slot the host zeroed for
 // this call) -> a one-workgroup launch stores them itself, a larger grid writes per-workgroup partials
@@ -146,7 +146,7 @@ uint32_t xsk_gpu__num_cu(int device) {
 static int echo_launch(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n, uint32_t opts,
                        uint8_t* d_verdicts, struct xsk_gpu_rec* d_recs, struct xsk_gpu_stats* d_stats,
                        void* d_workspace, void* stream, int hoststats, uint32_t tile, uint32_t grid_force = 0) {
-    if (opts & ~XSK_GPU_OPT_ALL) return -EINVAL;
+    if (opts & ~XSK_GPU_OPT_MASK) return -EINVAL;  // (0x8 is reserved)
     if (n == 0) return 0;
     if (n > XSK_GPU_MAX_BATCH) return -EINVAL;
     if (!d_umem || !d_descs || ((uintptr_t)d_umem & 15u) || (umem_size & 15u) || ((uintptr_t)d_descs & 15u) ||
@@ -223,7 +223,9 @@ static int echo_launch(void* d_umem, uint64_t umem_size, const struct xsk_gpu_de
         pa.recs = d_recs ? d_recs + i0 : nullptr;
         uint32_t pg = grid, ptw = tiles_per_wg;
         if (pieces > 1) echo6_geometry(pa.n, grid_force ? grid_force : ncu, &pg, &ptw);
-        if (opts == 0 && !small)
+        if (opts & XSK_GPU_OPT_IPV6)  // dual stack: wire mode that also answers ICMPv6 echo requests (xsk_echo_ds.hip)
+            xsk_gpu__echo_ds_launch(&pa, pg, ptw, small, s);
+        else if (opts == 0 && !small)
             echo_round_kernel<false, false><<<dim3(pg), dim3(kThreads6), 0, s>>>(pa, ptw);
         else if (opts == 0)  // rounds of sub-tiles, writes as soon as a wave has read
             echo_round_kernel<false, true><<<dim3(pg), dim3(kThreads6), 0, s>>>(pa, ptw);

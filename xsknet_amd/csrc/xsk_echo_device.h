@@ -605,7 +605,184 @@ __device__ __forceinline__ uint64_t sum_row_range(const uint8_t* rb, uint32_t lo
     return acc;
 }
 
-template <bool HB = false>
+// ICMPv6 echo (XSK_GPU_OPT_IPV6; spec: include/xsk_gpu.h): the rest of the wire header phase for a frame whose inner
+// ethertype is 0x86DD, l3 = 14 + 4 * tags, l4 = l3 + 40.  h[0..9]: the frame's first 40 bytes (wire_header_phase64).
+// The checksum covers the RFC 8200 §8.1 pseudo-header -- the two addresses, the message length, 58 -- and the message;
+// the addresses lie right in front of the message, so an untagged frame whose message ends at len ("plain") sums
+// bytes [22, len): the stream's [34, len) plus [22, 34) from h[].  An aligned plain frame (off = 0) has all 62 header
+// bytes in its window: dwords 10-15 join h[] in registers, the address sum comes from them and the reply is patched in
+// LDS by dword shuffles.  Behind a tag or an unaligned start the addresses and the ICMPv6 header may lie past the
+// window (off + l4 + 4 reaches 81): those bytes are read and written in the UMEM (fb(), byte-exact store), and tagged
+// or padded frames re-read their sums (sum_row_range), as the IPv4 frames do.  LDS is never indexed past row + 64.
+__device__ __forceinline__ bool wire_v6_phase(const EchoArgs& a, uint8_t* row, const uint32_t* h, uint32_t ic_raw,
+                                              uint64_t addr, uint32_t len, bool live, uint32_t wend, uint32_t l3,
+                                              uint32_t tags, Counters& cnt, u32x4* rec_out, uint32_t* verd_out) {
+    const bool strict = (a.opts & XSK_GPU_OPT_STRICT_IPV4) != 0u;
+    const bool verify = (a.opts & XSK_GPU_OPT_VERIFY_CSUM) != 0u;
+    const uint32_t off = (uint32_t)addr & 15u;
+    uint8_t* p = row + off;
+    uint8_t* pkt = a.umem + addr;
+    // frame byte i (i < len, so inside the UMEM): the window, or memory behind it
+    auto fb = [&](uint32_t i) -> uint32_t { return off + i < (uint32_t)kWin ? (uint32_t)p[i] : (uint32_t)pkt[i]; };
+    auto hb = [&](uint32_t i) -> uint32_t { return (h[i >> 2] >> (8u * (i & 3u))) & 0xFFu; };  // i < 40, constant
+    const uint32_t l4 = l3 + 40u;
+    uint32_t verdict = XSK_GPU_TX_REPLY, end = len, vihl = 0;
+    bool hdrs = false;
+    // the IPv6 gates after the tags (untagged: the fixed header's fields and both addresses' first bytes from h[])
+    auto ipv6_gates = [&](auto at) {
+        constexpr bool PL = decltype(at)::kPlain;
+        auto B = [&](uint32_t k) -> uint32_t { return PL ? hb(14u + k) : fb(l3 + k); };  // k <= 24
+        bool bad = false;
+        vihl = B(0);
+        if (strict) {
+            const uint32_t plen = (B(4) << 8) | B(5);
+            if ((vihl >> 4) != 6u || plen < 8u || l4 + plen > len || B(8) == 0xFFu || B(24) == 0xFFu) bad = true;
+            else end = l4 + plen;
+        }
+        if (bad) verdict = XSK_GPU_DROP_BAD_IP;
+        else if (B(6) != 58u) verdict = XSK_GPU_DROP_NOT_ICMP;
+        else if (len < l4 + 8u) verdict = XSK_GPU_DROP_SHORT;
+        else hdrs = true;
+    };
+    if (len < l4) verdict = XSK_GPU_DROP_SHORT;
+    else if (tags == 0u) ipv6_gates(WireAt14{});
+    else ipv6_gates(WireAtL3{});
+
+    const bool regs = tags == 0u && off == 0u;  // all 62 header bytes in the window: dwords 10-15 in e[]
+    uint32_t e[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    uint32_t ip_sum = 0, ic_sum = 0, itype = 0, icode = 0, csum_in = 0, flags = 0;
+    if (hdrs) {
+        if (regs) {
+            const uint2 q0 = *(const uint2*)(row + 40);
+            const u32x4 q1 = *(const u32x4*)(row + 48);
+            e[0] = q0.x, e[1] = q0.y, e[2] = q1.x, e[3] = q1.y, e[4] = q1.z, e[5] = q1.w;
+        }
+        // network-order folded sums: ad = the addresses [l3 + 8, l4), am = addresses and message [l3 + 8, end);
+        // tail = the pseudo-header's length (two 16-bit words) and next-header words
+        const uint32_t mlen = end - l4;
+        const uint32_t tail = (mlen >> 16) + (mlen & 0xFFFFu) + 58u;
+        const uint8_t* rb = a.umem + (addr & ~15ull);
+        const bool even = !((uint32_t)addr & 1u);
+        uint32_t ad, am;
+        if (regs) {
+            uint32_t acc = dot2_halves(h[5] >> 16, dot2_halves(h[6], dot2_halves(h[7], dot2_halves(h[8], 0u))));
+            acc = dot2_halves(h[9], dot2_halves(e[0], dot2_halves(e[1], dot2_halves(e[2], acc))));
+            ad = bswap16(fold32(dot2_halves(e[3] & 0xFFFFu, acc)));
+        } else {
+            ad = fold64(sum_row_range(rb, off + l3 + 8u, off + l4));
+            if (even) ad = bswap16(ad);
+        }
+        if (tags == 0u && end == len) {
+            // plain: [34, len) from the stream (absolute-alignment domain), [22, 34) from the frame-relative dwords
+            uint32_t st = fold32(ic_raw);
+            if (even) st = bswap16(st);
+            const uint32_t acc = dot2_halves(h[5] >> 16, dot2_halves(h[6], dot2_halves(h[7], dot2_halves(h[8] & 0xFFFFu, 0u))));
+            am = st + bswap16(fold32(acc));
+        } else {  // tags or padding: re-read the message
+            uint32_t ms = fold64(sum_row_range(rb, off + l4, off + end));
+            if (even) ms = bswap16(ms);
+            am = ad + ms;
+        }
+        ip_sum = fold32(ad + tail);
+        ic_sum = fold32(am + tail);
+        if (regs) {
+            itype = (e[3] >> 16) & 0xFFu;
+            icode = e[3] >> 24;
+            csum_in = bswap16(e[4]);
+        } else {
+            itype = fb(l4);
+            icode = fb(l4 + 1u);
+            csum_in = (fb(l4 + 2u) << 8) | fb(l4 + 3u);
+        }
+        flags = XSK_GPU_F_IPV6;
+        if (ic_sum == 0xFFFFu) flags |= XSK_GPU_F_ICMP_CSUM_OK;
+        if (tags) flags |= XSK_GPU_F_VLAN;
+        if (itype != 128u || (strict && icode != 0u)) verdict = XSK_GPU_DROP_NOT_ECHO;
+        else if (verify && ic_sum != 0xFFFFu) verdict = XSK_GPU_DROP_BAD_CSUM;
+    }
+    const bool tx = hdrs && verdict == XSK_GPU_TX_REPLY;
+    uint32_t csum_out = csum_in;
+    bool wb = false;
+    if (tx) {
+        // csum_replace2(&csum, 128, 129) on the LE-loaded field (xsk_receive.c:101-111): the 8 -> 0 closed form
+        // with ~old = 0xFF7F and new = 129
+        const uint32_t csum_le = bswap16(csum_in);
+        uint32_t c16 = (~csum_le) & 0xFFFFu;
+        c16 = (c16 + 0xFF7Fu) & 0xFFFFu;
+        c16 = (c16 + (c16 < 0xFF7Fu ? 1u : 0u)) & 0xFFFFu;
+        c16 = (c16 + 129u) & 0xFFFFu;
+        c16 = (c16 + (c16 < 129u ? 1u : 0u)) & 0xFFFFu;
+        const uint32_t csum_new_le = (~c16) & 0xFFFFu;
+        csum_out = bswap16(csum_new_le);
+        if (regs && wend >= (uint32_t)kWin) {
+            // aligned and untagged: MACs as in header_phase_ref, the addresses [22, 38) <-> [38, 54), type, checksum;
+            // patched in LDS, stored as a whole window in the write phase (l4 + 4 = 58 <= 64)
+            uint32_t* r32 = (uint32_t*)row;
+            *(u32x4*)row = u32x4{(h[1] >> 16) | (h[2] << 16), (h[2] >> 16) | (h[0] << 16), (h[0] >> 16) | (h[1] << 16), h[3]};
+            r32[5] = (h[5] & 0xFFFFu) | (h[9] & 0xFFFF0000u);                         // nh hlim | d0 d1
+            r32[6] = e[0];                                                            // d2 .. d13
+            r32[7] = e[1];
+            *(u32x4*)(row + 32) = u32x4{e[2], (e[3] & 0xFFFFu) | (h[5] & 0xFFFF0000u), h[6], h[7]};  // d14 d15 | s0 s1, s2 ..
+            r32[12] = h[8];                                                           // .. s13
+            r32[13] = (h[9] & 0xFFFFu) | (129u << 16) | (e[3] & 0xFF000000u);         // s14 s15 | type = 129 | code
+            r32[14] = (e[4] & 0xFFFF0000u) | csum_new_le;
+            wb = true;
+        } else if (off == 0u && l4 + 4u <= (uint32_t)kWin && wend >= (uint32_t)kWin) {
+            // aligned behind one tag (l4 + 4 = 62): byte swaps in LDS, whole 64-B sector stored in the write phase
+            // (rare traffic: rolled loops, here and below, keep the round body small enough to unroll over its tiles)
+#pragma nounroll
+            for (int i = 0; i < 6; ++i) {
+                const uint8_t x = p[i];
+                p[i] = p[6 + i];
+                p[6 + i] = x;
+            }
+#pragma nounroll
+            for (int i = 0; i < 16; ++i) {
+                const uint8_t x = p[l3 + 8 + i];
+                p[l3 + 8 + i] = p[l3 + 24 + i];
+                p[l3 + 24 + i] = x;
+            }
+            p[l4] = 129;
+            p[l4 + 2] = (uint8_t)csum_new_le;
+            p[l4 + 3] = (uint8_t)(csum_new_le >> 8);
+            wb = true;
+        } else {  // byte-exact: only the rewritten bytes, read from the window or (behind it) the UMEM
+#pragma nounroll
+            for (int i = 0; i < 6; ++i) {
+                const uint32_t x = fb(i), y = fb(6 + i);
+                pkt[i] = (uint8_t)y;
+                pkt[6 + i] = (uint8_t)x;
+            }
+#pragma nounroll
+            for (int i = 0; i < 16; ++i) {
+                const uint32_t x = fb(l3 + 8 + i), y = fb(l3 + 24 + i);
+                pkt[l3 + 8 + i] = (uint8_t)y;
+                pkt[l3 + 24 + i] = (uint8_t)x;
+            }
+            pkt[l4] = 129;
+            pkt[l4 + 2] = (uint8_t)csum_new_le;
+            pkt[l4 + 3] = (uint8_t)(csum_new_le >> 8);
+        }
+    }
+    u32x4 r;
+    r.x = verdict | (flags << 8) | ((hdrs ? 58u : 0u) << 16) | (itype << 24);
+    r.y = icode | ((hdrs ? vihl : 0u) << 8) | ((hdrs ? 0x86DDu : 0u) << 16);
+    r.z = csum_in | (csum_out << 16);
+    r.w = ip_sum | (ic_sum << 16);
+    *rec_out = r;
+    *verd_out = verdict;
+    if (live) {
+        cnt.rxp += 1;
+        cnt.rxb += len;
+        if (tx) {
+            cnt.txp += 1;
+            cnt.txb += len;
+        }
+    }
+    return wb;
+}
+
+template <bool HB = false, bool V6 = false>
 __device__ __forceinline__ bool wire_header_phase64(const EchoArgs& a, uint8_t* row, uint32_t ic_raw, uint64_t addr,
                                                     uint32_t len, bool ok, bool live, uint32_t wend, Counters& cnt,
                                                     u32x4* rec_out, uint32_t* verd_out) {
@@ -635,6 +812,7 @@ __device__ __forceinline__ bool wire_header_phase64(const EchoArgs& a, uint8_t* 
     uint32_t verdict = XSK_GPU_TX_REPLY;
     uint32_t l3 = 14, hl = 20, end = len, et = 0, tags = 0;
     bool hdrs = false;
+    bool v6 = false;  // V6 kernels: an inner ethertype of 0x86DD under XSK_GPU_OPT_IPV6 (wire_v6_phase)
     // the IPv4 / ICMP gates after the tags (untagged: l3 = 14, every byte from h[])
     auto ipv4_gates = [&](auto at) {
         constexpr bool PL = decltype(at)::kPlain;
@@ -676,10 +854,14 @@ __device__ __forceinline__ bool wire_header_phase64(const EchoArgs& a, uint8_t* 
             }
         }
         if (cut) verdict = XSK_GPU_DROP_SHORT;
+        else if (V6 && et == 0x86DDu && (a.opts & XSK_GPU_OPT_IPV6)) v6 = true;
         else if (et != 0x0800u) verdict = XSK_GPU_DROP_NOT_IPV4;
         else if (len < l3 + 20) verdict = XSK_GPU_DROP_SHORT;
         else if (tags == 0u) ipv4_gates(WireAt14{});
         else ipv4_gates(WireAtL3{});
+    }
+    if constexpr (V6) {
+        if (v6) return wire_v6_phase(a, row, h, ic_raw, addr, len, live, wend, l3, tags, cnt, rec_out, verd_out);
     }
     const uint32_t l4 = l3 + hl;
     const bool std34 = tags == 0u && hl == 20u;  // l3 = 14, l4 = 34: the reference's offsets
@@ -851,7 +1033,7 @@ __device__ __forceinline__ FrameIn frame_in(const EchoArgs& a, u32x4 dsc, bool i
 // round pays two memory round trips instead of four, with twice the bytes in flight.  The windows go to the
 // two LDS slots, the ICMP sums to the two sum rows, then the header phase of each tile.  Returns false
 // (nothing written) when either tile has a longer frame.
-template <int HEAVY, bool WIRE, bool HB = false>
+template <int HEAVY, bool WIRE, bool HB = false, bool V6 = false>
 __device__ __forceinline__ bool read_round_short2(const EchoArgs& a, uint32_t t0, uint32_t t1, uint8_t* rows0,
                                                   uint8_t* rows1, uint32_t* sums0, uint32_t* sums1, uint32_t lane,
                                                   Counters& cnt, u32x4* rec, uint32_t* verd, uint32_t* alo,
@@ -909,12 +1091,12 @@ __device__ __forceinline__ bool read_round_short2(const EchoArgs& a, uint32_t t0
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    bool wb = WIRE ? wire_header_phase64<HB>(a, rows0 + lane * kWin, sums0[lane], F0.addr, F0.len, F0.ok, in0, F0.wend, cnt,
+    bool wb = WIRE ? wire_header_phase64<HB, V6>(a, rows0 + lane * kWin, sums0[lane], F0.addr, F0.len, F0.ok, in0, F0.wend, cnt,
                                          &rec[0], &verd[0])
                    : header_phase_ref<HB>(a, rows0 + lane * kWin, sums0[lane], F0.addr, F0.len, in0, F0.ok, F0.parse, cnt,
                                       &rec[0], &verd[0]);
     wbm[0] = __ballot(wb);
-    wb = WIRE ? wire_header_phase64<HB>(a, rows1 + lane * kWin, sums1[lane], F1.addr, F1.len, F1.ok, in1, F1.wend, cnt, &rec[1],
+    wb = WIRE ? wire_header_phase64<HB, V6>(a, rows1 + lane * kWin, sums1[lane], F1.addr, F1.len, F1.ok, in1, F1.wend, cnt, &rec[1],
                                     &verd[1])
               : header_phase_ref<HB>(a, rows1 + lane * kWin, sums1[lane], F1.addr, F1.len, in1, F1.ok, F1.parse, cnt, &rec[1],
                                  &verd[1]);
@@ -952,13 +1134,14 @@ __device__ __forceinline__ bool read_round_short2(const EchoArgs& a, uint32_t t0
 //   TRACE wave 0 stamps the body's phase boundaries into a.trace (the low-latency kernel's diagnostics)
 //   DLDS  the descriptors may already be in the LDS (a.desc_in_lds, the low-latency kernel's first poll)
 //   WT    write-phase windows and records stored write-through (sc1 raw buffer stores)
+//   V6    the dual-stack kernels (XSK_GPU_OPT_IPV6): wire mode whose header phase also answers ICMPv6 echo requests
 // The per-tile stream choices: tiles whose frames all fit their 64-B windows (c2)
 // skip the row stream (and two such tiles of a round are read together, PAIR), ping-size tiles (every frame
 // within 128 B) are read by 8-lane groups, uniform long tiles (c3, c5) take masks computed once per tile,
 // ragged tiles (c4) the ranked step-packed streams.
 // ================================================================================================
 template <int TPW, int SYNC, bool WIRE, bool SUBT, bool TRACE, bool DLDS, bool WT, int HEAVY, int UR = kU,
-          bool USPLIT = false, bool PRIO = false, int SLACK = 0, bool HB = false>
+          bool USPLIT = false, bool PRIO = false, int SLACK = 0, bool HB = false, bool V6 = false>
 __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, uint32_t t_end, Echo6Smem<TPW>& sm) {
     static_assert(SYNC == 0 || SYNC == 2, "write phases: at once (0) or heavy waves wait for the round (2)");
     static_assert(SLACK >= 0 && SLACK < kWaves6, "SLACK: waves a heavy wave does not wait for");
@@ -988,7 +1171,7 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
         // ================= read phase =================
         bool paired = false;
         if (PAIR && r0 + wave < t_end && r0 + (uint32_t)kWaves6 + wave < t_end)  // wave-uniform
-            paired = read_round_short2<HEAVY, WIRE, HB>(a, r0 + wave, r0 + (uint32_t)kWaves6 + wave, s_hdr[wave][0],
+            paired = read_round_short2<HEAVY, WIRE, HB, V6>(a, r0 + wave, r0 + (uint32_t)kWaves6 + wave, s_hdr[wave][0],
                                               s_hdr[wave][TPW > 1 ? 1 : 0], sm.sum[wave][0], sm.sum[wave][1], lane,
                                               cnt, rec, verd, alo, ahi, wbm, round_long);
 #pragma unroll
@@ -1155,7 +1338,7 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
                 const uint32_t ic_raw = nit ? sums_ic[lane] : 0u;
                 bool wb;
                 if (WIRE)
-                    wb = wire_header_phase64<HB>(a, rows + lane * kRowW, ic_raw, addr, len, ok, in_n, wend, cnt, &rec_o,
+                    wb = wire_header_phase64<HB, V6>(a, rows + lane * kRowW, ic_raw, addr, len, ok, in_n, wend, cnt, &rec_o,
                                              &verd_o);
                 else
                     wb = header_phase_ref<HB>(a, rows + lane * kWin, ic_raw, addr, len, in_n, ok, parse, cnt, &rec_o,

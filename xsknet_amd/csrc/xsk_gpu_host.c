@@ -40,7 +40,7 @@
 #define CHUNK_FRAMES 32768u /* staged pipeline granule: ~49 MB of 1500-B frames per copy-in */
 #define TAIL_FRAMES 4096u   /* staged: the last chunks halve down to this, so the work left after the last copy-in
                              * (transform, pack, copy-back, host scatter of one chunk) is short */
-#define PACK 96u            /* staged: bytes per frame of the packed rewritten headers (wire mode <= 86) */
+#define PACK 96u            /* staged: bytes per frame of the packed rewritten headers (wire mode: IPv4 <= 86, IPv6 <= 66) */
 #define STAGE_HALF (32u << 20) /* staged without a mapped alias: default bytes per half of the host-pack staging */
 
 struct xsk_gpu_ctx {
@@ -405,11 +405,12 @@ out:
 }
 
 int xsk_gpu_set_options(xsk_gpu_ctx* c, uint32_t opts) {
-    if (!c || (opts & ~XSK_GPU_OPT_ALL)) return -EINVAL;
+    if (!c || (opts & ~XSK_GPU_OPT_MASK)) return -EINVAL;
     if (c->pend_n) return -EBUSY; /* the batch in flight runs under the options it was submitted with */
     if (c->ll) {
         (void)hipSetDevice(c->device);
-        const int rc = xsk_gpu__lowlat_set_opts(c->ll, opts);
+        /* (the resident kernel has no IPv6 instance: with XSK_GPU_OPT_IPV6 every batch is launched, xsk_gpu__submit) */
+        const int rc = xsk_gpu__lowlat_set_opts(c->ll, opts & XSK_GPU_OPT_ALL);
         if (rc) return rc;
     }
     c->opts = opts;
@@ -601,7 +602,8 @@ int xsk_gpu__submit(xsk_gpu_ctx* c, const struct xsk_gpu_desc* descs, uint32_t n
          * until it has (-EBUSY), then the context is usable again */
         if (!xsk_gpu__lowlat_recover(c->ll)) return -EBUSY;
     }
-    if (c->ll && n <= XSK_GPU_LOWLAT_MAX && !no_doorbell) { /* the doorbell: no launch, no sync, no HIP call */
+    /* the doorbell: no launch, no sync, no HIP call (never with XSK_GPU_OPT_IPV6: the resident kernel parses IPv4 only) */
+    if (c->ll && n <= XSK_GPU_LOWLAT_MAX && !no_doorbell && !(c->opts & XSK_GPU_OPT_IPV6)) {
         memcpy(xsk_gpu__lowlat_descs(c->ll), descs, (size_t)n * sizeof *descs);
         uint32_t w = 0;
         rc = xsk_gpu__lowlat_post(c->ll, n, want_recs, &w);
@@ -724,7 +726,7 @@ int xsk_gpu__complete(xsk_gpu_ctx* c, uint8_t* verdicts, struct xsk_gpu_rec* rec
         if (staged) { /* scatter the rewritten bytes of this chunk's replies */
             for (uint32_t i = i0; i < i0 + m; i++) {
                 if (c->h_verd[i] != XSK_GPU_TX_REPLY) continue;
-                /* reference mode rewrites bytes [0, 38); wire mode bytes below l4 + 4 <= 86 <= len */
+                /* reference mode rewrites bytes [0, 38); wire mode bytes below l4 + 4 <= 86 <= len (IPv6: <= 66) */
                 const uint32_t w = c->opts ? (descs[i].len < PACK ? descs[i].len : PACK) : 38u;
                 memcpy(c->umem + descs[i].addr, c->h_pack + (size_t)i * PACK, w);
             }

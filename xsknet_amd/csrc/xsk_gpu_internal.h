@@ -64,6 +64,11 @@ XSK_GPU__HIDDEN int xsk_gpu__stage_unpack_dev(const void* d_stage, const uint32_
                                               uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
                                               uint32_t wire, void* stream);
 
+/* xsk_echo_ds.hip: launch the dual-stack transform kernel (XSK_GPU_OPT_IPV6) for echo_launch() of xsk_echo.hip.
+ * args: echo_launch's EchoArgs (xsk_echo_device.h); the launch's outcome is left in hipGetLastError(). */
+XSK_GPU__HIDDEN void xsk_gpu__echo_ds_launch(const void* args, uint32_t grid, uint32_t tiles_per_wg, int small,
+                                             void* stream);
+
 /* xsk_echo.hip: xsk_gpu_echo_dev_opts for counters in mapped host memory (no device atomics): d_stats
  * must be a slot zeroed for this call (a one-workgroup launch stores the counters without reading it).
  * tile: frames per wave of a small batch (xsk_gpu__small_tile), 0 = ceil(n / 16). */

@@ -55,6 +55,7 @@ struct xsk_gpu_multi {
     struct xsk_gpu_rec* job_recs;
     int job_launch; /* every share takes the launch path (a share above XSK_GPU_LOWLAT_MAX, or not every context
                      * runs LOWLAT) */
+    uint32_t opts;  /* the options every context runs under (xsk_gpu_multi_set_options) */
     int all_lowlat; /* every context really runs XSK_GPU_MODE_LOWLAT (none was downgraded at init) */
     int status[XSK_GPU_MULTI_MAX]; /* per-context result of the last xsk_gpu_multi_process */
 };
@@ -186,11 +187,12 @@ fail:
 }
 
 int xsk_gpu_multi_set_options(xsk_gpu_multi* m, uint32_t opts) {
-    if (!m || (opts & ~XSK_GPU_OPT_ALL)) return -EINVAL;
+    if (!m || (opts & ~XSK_GPU_OPT_MASK)) return -EINVAL;
     for (uint32_t g = 0; g < m->G; g++) {
         const int rc = xsk_gpu_set_options(m->w[g].ctx, opts);
         if (rc) return rc;
     }
+    m->opts = opts;
     return 0;
 }
 
@@ -207,7 +209,8 @@ int xsk_gpu_multi_process(xsk_gpu_multi* m, const struct xsk_gpu_desc* descs, ui
      * every context runs LOWLAT (a LOWLAT request beyond the device's resident-kernel cap runs as ZEROCOPY) and every
      * share fits it; otherwise every context takes the launch path, and every resident kernel has stopped before
      * any share is launched, so no share runs beside a resident kernel that holds a CU */
-    m->job_launch = !m->all_lowlat || (n + m->G - 1) / m->G > XSK_GPU_LOWLAT_MAX;
+    /* (XSK_GPU_OPT_IPV6: the resident kernel has no IPv6 instance, so such contexts count as launched) */
+    m->job_launch = !m->all_lowlat || (m->opts & XSK_GPU_OPT_IPV6) || (n + m->G - 1) / m->G > XSK_GPU_LOWLAT_MAX;
     /* (with a downgraded context no batch ever takes a doorbell, so no resident kernel is ever started: nothing to
      * stop, per call or otherwise -- ADVICE r04) */
     if (m->job_launch && m->all_lowlat)

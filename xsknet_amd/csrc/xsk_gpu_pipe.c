@@ -195,7 +195,7 @@ int xsk_gpu_rx_pipe_flush(xsk_gpu_rx_pipe* p, struct xsk_gpu_ring* tx, struct xs
 }
 
 int xsk_gpu_rx_pipe_set_options(xsk_gpu_rx_pipe* p, uint32_t opts) {
-    if (!p || (opts & ~XSK_GPU_OPT_ALL)) return -EINVAL;
+    if (!p || (opts & ~XSK_GPU_OPT_MASK)) return -EINVAL;
     if (p->count) return -EBUSY;
     for (uint32_t i = 0; i < p->depth; i++) {
         const int rc = xsk_gpu_set_options(p->s[i].ctx, opts);
