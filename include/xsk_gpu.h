@@ -43,7 +43,10 @@ extern "C" {
 
 #define XSK_GPU_ABI_VERSION 1
 
-/* Descriptors with len above this are DROP_BAD_DESC (AF_XDP frames are <= one UMEM chunk). */
+/* Descriptors with len above this are DROP_BAD_DESC (AF_XDP frames are <= one UMEM chunk).  Every length up to it
+ * is supported: verdicts, records (both RFC 1071 sums) and rewritten bytes are exact for any accepted frame.  The
+ * kernels' fastest stream for tiles of 64 equal frames sums in 32 bits and is taken only while addr % 16 + len
+ * <= 64 KiB; longer frames run on the streams with 64-bit sums (tests/test_gpu_long_frames.py: up to 2 MiB). */
 #define XSK_GPU_MAX_LEN (1u << 30)
 
 /* Frames per wavefront tile == RX_BATCH_SIZE (src/lib/xsk_utils.h:8). */

@@ -664,16 +664,31 @@ def test_more_tiles_than_grid():
     assert torch.equal(before, d_umem)
 
 
-@pytest.mark.parametrize("mode,lo,hi,opts", [(1, 20, 1500, 0), (0, 1500, 1500, 0), (1, 20, 1500, 7), (0, 1500, 1500, 7)])
+@pytest.mark.parametrize("mode,lo,hi,opts", [(1, 20, 1500, 0), (0, 1500, 1500, 0), (1, 20, 1500, 7), (0, 1500, 1500, 7),
+                                             (1, 20, 1500, 0x17), (0, 1500, 1500, 0x17)])
 def test_tile_spanning_more_than_2gib(mode, lo, hi, opts):
     """Frames of one tile more than 2 GiB apart (the kernel's 64-bit-address path): ragged tiles take the
-    sorted streams, uniform 1500-B tiles the per-step streams; reference and wire mode."""
-    dev = _dev()
+    sorted streams, uniform 1500-B tiles the per-step streams; reference mode, wire mode and the dual-stack kernel
+    (0x17: IPv4 traffic only, so the C oracle's wire mode is the reference; the mixed generator's 0x86DD frames
+    are emptied to len 0, as in test_v6_ipv4_traffic_equals_the_oracle)."""
+    from tests.stream_paths import sub_tile_live, tile_paths
+    from tests.v6_frames import G6
     size = (2 << 30) + (512 << 20)  # 2.5 GiB UMEM
     far = (2 << 30) + (64 << 20)
     n = 200
     tmp = np.zeros(n * 2048, np.uint8)
     src = oracle.synth_batch(tmp, n, 0, 2048, seed=0x5EED1212, mode=mode, len_lo=lo, len_hi=hi)
+    if opts & 0x10:
+        for i in range(n):
+            if G6.v6_l3(tmp[i * 2048:(i + 1) * 2048].tobytes(), int(src[i]["len"]), opts) is not None:
+                src[i]["len"] = 0
+        assert all(G6.v6_l3(tmp[i * 2048:(i + 1) * 2048].tobytes(), int(src[i]["len"]), opts) is None for i in range(n))
+    far_descs = np.zeros(n, X.DESC_DTYPE)
+    far_descs["addr"] = [(far if i % 2 else 0) + i * 2048 + (i % 5) for i in range(n)]
+    far_descs["len"] = src["len"]
+    # (200 frames: the sub-tile kernel, 4-frame tiles, each with frames on both sides of the 2 GiB gap)
+    assert ("sorted_far" if mode else "per_step_far") in tile_paths(far_descs, size, opts != 0, sub_tile_live(n, 0))
+    dev = _dev()
     d_umem = torch.zeros(size, dtype=torch.uint8, device=dev)
     descs = np.zeros(n, X.DESC_DTYPE)
     for i in range(n):
@@ -693,7 +708,7 @@ def test_tile_spanning_more_than_2gib(mode, lo, hi, opts):
     img[n * 2048 + 64:] = hi_before
     hd = descs.copy()
     hd["addr"] = np.where(np.arange(n) % 2 == 1, descs["addr"] - far + n * 2048 + 64, descs["addr"])
-    v_ref, r_ref, _ = oracle.echo_batch_opts(img, hd, opts)
+    v_ref, r_ref, _ = oracle.echo_batch_opts(img, hd, opts & 7)
     assert (verd.cpu().numpy() == v_ref).all()
     assert (recs.cpu().numpy().view(X.REC_DTYPE) == r_ref).all()
     assert (d_umem[:n * 2048 + 64].cpu().numpy() == img[:n * 2048 + 64]).all()

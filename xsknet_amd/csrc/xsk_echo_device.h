@@ -22,6 +22,7 @@ constexpr int kWin = 64;                    // header window [a16, a16 + 64), re
 constexpr uint32_t kMaxLen = 1u << 30;      // build-added descriptor sanity bound (XSK_GPU_MAX_LEN)
 constexpr int kWaves6 = 16;                 // waves per workgroup (one workgroup per CU)
 constexpr int kThreads6 = kWaves6 * 64;     // 1024
+constexpr uint32_t kUniMaxNit = 256;        // longest tile of stream_tile_uniform, in row-loads (its 32-bit sums)
 constexpr int kU = 4;                       // 256-B row-loads in flight per lane in the row streams
 constexpr int kUR = 6;                      // the same for the launched kernel's ranked (ragged-tile) streams:
                                             // c4 185.4 -> 182.6 us, c3 / p98 unchanged (profiles/r03/ab_ranked_u6_u8_*)
@@ -391,9 +392,11 @@ __device__ __forceinline__ void stream_tile_sorted(const EchoArgs& a, __amdgpu_b
 // the ICMP byte range [lo, hi) = [off + 34, off + len) is the same in every row.  A lane's byte masks are
 // then the same for every step: computed once per tile for the first and the last row-load (the only blocks
 // the range can cut; the others are whole or, past `lim`, not loaded), and a step costs its loads, one
-// v_dot2_u32_u16 per dword, two masks and the row reduction.  The sums are plain 32-bit sums of 16-bit halves
-// (< 2^32 for frames <= 64 KiB: 257 blocks x 8 halves x 65535 x 16 lanes); the IPv4 header sum comes from the
-// window in the header phase.
+// v_dot2_u32_u16 per dword, two masks and the row reduction.  The sums are plain 32-bit sums of 16-bit halves: a
+// row total is at most ns row-loads x 16 lanes x 8 halves x 65535, which stays below 2^32 only while ns <= 512, so
+// the caller takes this path for ns <= kUniMaxNit = 256 row-loads (off + len <= 64 KiB: at most 0x7FFF8000) and
+// sends longer uniform tiles to the per-step streams, which flush their halves into 64-bit sums.  The IPv4 header
+// sum comes from the window in the header phase.
 template <int U, bool SPLIT = false, bool PRIO = false>
 __device__ __forceinline__ void stream_tile_uniform(__amdgpu_buffer_rsrc_t rsrc, const FrameMeta6* meta, uint8_t* rows,
                                                     uint32_t* sums_ic, uint32_t ns, uint32_t lo, uint32_t hi,
@@ -1301,7 +1304,9 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
                         // ragged tile (or one too short to fill a batch of U row-loads): ranked streams
                         if (fast) stream_tile_sorted<UR, true, true, PRIO>(a, ld.r, meta, sm.sort[wave], rows, sums_ic, nit, lane);
                         else stream_tile_sorted<UR, false, true, PRIO>(a, ld.r, meta, sm.sort[wave], rows, sums_ic, nit, lane);
-                    } else if (fast && __ballot(!parse) == 0ull && __ballot(ukey != uniform(ukey)) == 0ull) {
+                    } else if (fast && uniform(max_nit_lane(nit)) <= kUniMaxNit && __ballot(!parse) == 0ull &&
+                               __ballot(ukey != uniform(ukey)) == 0ull) {
+                        // (longer uniform tiles take the per-step streams below, whose sums are 64-bit)
                         stream_tile_uniform<U, USPLIT, PRIO>(ld.r, meta, rows, sums_ic, uniform(nit), uniform(off) + 34u,
                                                              uniform(rowhi), lane);
                     } else {
