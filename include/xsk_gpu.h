@@ -163,8 +163,7 @@ enum xsk_gpu_verdict {
 /* Limitations: XSK_GPU_OPT_MASK is every valid bit; 0x8 is reserved and rejected (-EINVAL).    */
 /* The resident XSK_GPU_MODE_LOWLAT kernel has no IPv6 instance: a LOWLAT context with          */
 /* XSK_GPU_OPT_IPV6 set serves every batch through the launch path (same results, a launch per  */
-/* batch; xsk_gpu_ctx_mode() still reports LOWLAT).  xsk_gpu_classify_dev still passes 0x86DD   */
-/* to the kernel stack.                                                                         */
+/* batch; xsk_gpu_ctx_mode() still reports LOWLAT).                                             */
 /* ------------------------------------------------------------------------------------------ */
 #define XSK_GPU_OPT_IPV6 0x10u /* wire mode also answers ICMPv6 echo requests */
 #define XSK_GPU_OPT_MASK 0x17u /* every valid bit; 0x8 is reserved and rejected */
@@ -383,6 +382,40 @@ size_t xsk_gpu_classify_workspace_size(uint32_t n);
 int xsk_gpu_classify_dev(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
                          int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out, uint32_t* d_nout,
                          void* d_workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Ingress filter with wire-format options (build-added).  xsk_gpu_classify_dev_opts() takes   */
+/* the option word of xsk_gpu_echo_dev_opts(), so that a tagged or an IPv6 echo request reaches */
+/* the transform that answers it.  opts == 0 is xsk_gpu_classify_dev() exactly (the same        */
+/* kernels); opts & ~XSK_GPU_OPT_MASK is -EINVAL.  Per frame, for nonzero opts:                 */
+/*   1. DROP if len > XSK_GPU_MAX_LEN or [addr, addr + len) does not lie inside the UMEM (wire  */
+/*      mode's descriptor rule: nothing the transform calls DROP_BAD_DESC is passed or          */
+/*      redirected);                                                                            */
+/*   2. DROP if len < 14;                                                                       */
+/*   3. l3 = 14, et = be16(12); with XSK_GPU_OPT_VLAN, while fewer than two tags have been      */
+/*      skipped and et is 0x8100 or 0x88A8: DROP if len < l3 + 4 (a tag cut by the frame end),  */
+/*      else et = be16(l3 + 2), l3 += 4;                                                        */
+/*   4. et == 0x0800: DROP if len < l3 + 20; PASS if byte l3 + 9 != 1; else REDIRECT;           */
+/*   5. et == 0x86DD and XSK_GPU_OPT_IPV6: DROP if len < l3 + 40; PASS if byte l3 + 6 != 58     */
+/*      (extension headers are not walked, as in the transform); DROP if len < l3 + 48; PASS if */
+/*      byte l3 + 40 != 128; else REDIRECT.  Only echo requests leave the kernel stack:         */
+/*      neighbour discovery (133-137), MLD, errors and echo replies are ICMPv6 too, and a host  */
+/*      whose stack never sees a neighbour solicitation is not reachable over IPv6 at all;      */
+/*   6. anything else is PASS: a third tag, tags without XSK_GPU_OPT_VLAN, 0x86DD without       */
+/*      XSK_GPU_OPT_IPV6.                                                                       */
+/* REDIRECT becomes DROP when target_bound == 0.  XSK_GPU_OPT_STRICT_IPV4 and                   */
+/* XSK_GPU_OPT_VERIFY_CSUM are accepted and change no action: the filter decides who owns a     */
+/* frame, the socket or the kernel stack, and a malformed frame it redirects gets DROP_BAD_IP / */
+/* DROP_BAD_CSUM from the transform.  For untagged frames other than 0x86DD with valid          */
+/* descriptors this is xdp_sock_prog(); and for every option word, every frame the transform    */
+/* alone would answer (XSK_GPU_TX_REPLY) is REDIRECT.  Arguments, alignment rules, workspace    */
+/* (xsk_gpu_classify_workspace_size), n == 0 and the optional d_out / d_nout are those of       */
+/* xsk_gpu_classify_dev(); every argument is checked before any device call.  Reads only bytes  */
+/* of [addr, addr + len).  Asynchronous on `stream`.                                            */
+/* ------------------------------------------------------------------------------------------ */
+int xsk_gpu_classify_dev_opts(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
+                              uint32_t opts, int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out,
+                              uint32_t* d_nout, void* d_workspace, void* stream);
 
 /* The UMEM allocation for the host modes: the reference allocates its UMEM with posix_memalign(getpagesize(),
  * NUM_FRAMES * FRAME_SIZE) (src/lib/xsk_utils.c:132-135); this gives the same kind of memory (anonymous, private,

@@ -117,6 +117,7 @@ _SIGS = {
     "xsk_gpu_tx_complete": ([C.POINTER(Ring), C.POINTER(FramePool), C.c_uint32], C.c_uint32),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_multi_init": ([C.POINTER(_P), _P, C.c_uint32, _P, C.c_uint64, C.c_uint32, C.c_int], C.c_int),
     "xsk_gpu_multi_process": ([_P, _P, C.c_uint32, _P, _P, _P], C.c_int),
     "xsk_gpu_multi_set_options": ([_P, C.c_uint32], C.c_int),
@@ -238,12 +239,19 @@ def echo_dev(umem, descs, n: int, verdicts=None, recs=None, stats=None, workspac
 XDP_DROP, XDP_PASS, XDP_REDIRECT = 1, 2, 4
 
 
-def classify_dev(umem, descs, n: int, bound: bool, actions, out=None, nout=None, workspace=None, stream=None) -> None:
-    """xsk_gpu_classify_dev: the XDP ingress filter (inner_xdp.c:26-61) + in-order compaction."""
+def classify_dev(umem, descs, n: int, bound: bool, actions, out=None, nout=None, workspace=None, stream=None,
+                 opts: int = 0) -> None:
+    """xsk_gpu_classify_dev: the XDP ingress filter (inner_xdp.c:26-61) + in-order compaction.  Nonzero opts:
+    xsk_gpu_classify_dev_opts, the VLAN- and IPv6-aware filter in front of echo_dev(opts=...)."""
     if workspace is None:
         import torch
         workspace = torch.empty(int(lib().xsk_gpu_classify_workspace_size(max(n, 1))), dtype=torch.uint8,
                                 device=umem.device)
+    if opts:
+        _check("xsk_gpu_classify_dev_opts", lib().xsk_gpu_classify_dev_opts(
+            _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, opts, 1 if bound else 0, _ptr(actions),
+            _ptr(out), _ptr(nout), _ptr(workspace), _stream_ptr(stream)))
+        return
     _check("xsk_gpu_classify_dev", lib().xsk_gpu_classify_dev(
         _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, 1 if bound else 0, _ptr(actions), _ptr(out),
         _ptr(nout), _ptr(workspace), _stream_ptr(stream)))

@@ -9,9 +9,13 @@
 //   2. scan: one 1024-thread workgroup turns the per-workgroup counts into exclusive offsets and the
 //      total;
 //   3. scatter: lane per frame again — wave ballot prefix + workgroup offset -> output slot.
+//
+// xsk_gpu_classify_dev_opts() with nonzero options replaces launch 1 by classify_wire_kernel, the VLAN- and
+// IPv6-aware filter specified in include/xsk_gpu.h; launches 2 and 3 are the same.
 #include <errno.h>
 
 #include "../../include/xsk_gpu.h"
+#include "xsk_classify_wire.h"
 #include "xsk_echo_kernels.h"
 #include "xsk_hip_util.h"
 
@@ -48,6 +52,23 @@ __global__ __launch_bounds__(kCT) void classify_kernel(const uint8_t* umem, uint
     uint32_t act = 0;
     if (i < n) {
         act = classify_one(umem, umem_size, descs[i], bound);
+        actions[i] = (uint8_t)act;
+    }
+    const uint64_t m = __ballot(act == XSK_GPU_XDP_REDIRECT);
+    if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) wg_count[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// First stage for nonzero options: classify_wire_one() of xsk_classify_wire.h per lane, the same counts as above.
+__global__ __launch_bounds__(kCT) void classify_wire_kernel(const uint8_t* umem, uint64_t umem_size,
+                                                            const xsk_gpu_desc* descs, uint32_t n, uint32_t opts,
+                                                            int bound, uint8_t* actions, uint32_t* wg_count) {
+    __shared__ uint32_t s_w[kCT / 64];
+    const uint32_t i = blockIdx.x * kCT + threadIdx.x;
+    uint32_t act = 0;
+    if (i < n) {
+        act = classify_wire_one(umem, umem_size, descs[i], opts, bound);
         actions[i] = (uint8_t)act;
     }
     const uint64_t m = __ballot(act == XSK_GPU_XDP_REDIRECT);
@@ -103,9 +124,10 @@ extern "C" {
 
 size_t xsk_gpu_classify_workspace_size(uint32_t n) { return (size_t)((n + kCT - 1) / kCT + 1) * sizeof(uint32_t); }
 
-int xsk_gpu_classify_dev(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
-                         int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out, uint32_t* d_nout,
-                         void* d_workspace, void* stream) {
+// opts == 0: the reference's filter (classify_kernel); nonzero: classify_wire_kernel.  Same scan and scatter.
+static int classify_launch(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
+                           uint32_t opts, int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out,
+                           uint32_t* d_nout, void* d_workspace, void* stream) {
     if (n == 0) {
         if (d_nout) HIP_TRY(hipMemsetAsync(d_nout, 0, sizeof(uint32_t), (hipStream_t)stream));
         return 0;
@@ -116,8 +138,12 @@ int xsk_gpu_classify_dev(const void* d_umem, uint64_t umem_size, const struct xs
     const uint32_t nwg = (n + kCT - 1) / kCT;
     hipStream_t s = (hipStream_t)stream;
     uint32_t* wg = (uint32_t*)d_workspace;
-    hipLaunchKernelGGL(classify_kernel, dim3(nwg), dim3(kCT), 0, s, (const uint8_t*)d_umem, umem_size, d_descs, n,
-                       target_bound, d_actions, wg);
+    if (opts)
+        hipLaunchKernelGGL(classify_wire_kernel, dim3(nwg), dim3(kCT), 0, s, (const uint8_t*)d_umem, umem_size, d_descs,
+                           n, opts, target_bound, d_actions, wg);
+    else
+        hipLaunchKernelGGL(classify_kernel, dim3(nwg), dim3(kCT), 0, s, (const uint8_t*)d_umem, umem_size, d_descs, n,
+                           target_bound, d_actions, wg);
     HIP_TRY(hipGetLastError());
     if (d_out) {
         hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, wg, nwg, d_nout);
@@ -127,6 +153,21 @@ int xsk_gpu_classify_dev(const void* d_umem, uint64_t umem_size, const struct xs
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+
+int xsk_gpu_classify_dev(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
+                         int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out, uint32_t* d_nout,
+                         void* d_workspace, void* stream) {
+    return classify_launch(d_umem, umem_size, d_descs, n, 0, target_bound, d_actions, d_out, d_nout, d_workspace,
+                           stream);
+}
+
+int xsk_gpu_classify_dev_opts(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
+                              uint32_t opts, int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out,
+                              uint32_t* d_nout, void* d_workspace, void* stream) {
+    if (opts & ~XSK_GPU_OPT_MASK) return -EINVAL;
+    return classify_launch(d_umem, umem_size, d_descs, n, opts, target_bound, d_actions, d_out, d_nout, d_workspace,
+                           stream);
 }
 
 }  // extern "C"
