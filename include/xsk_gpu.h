@@ -161,9 +161,8 @@ enum xsk_gpu_verdict {
 /* that pseudo-header followed by the message (odd tail zero-padded).  Flags: F_IPV6 always,    */
 /* F_ICMP_CSUM_OK iff icmp_sum == 0xFFFF, F_VLAN as above; never F_IP_CSUM_OK / F_IP_OPTIONS.   */
 /* Limitations: XSK_GPU_OPT_MASK is every valid bit; 0x8 is reserved and rejected (-EINVAL).    */
-/* The resident XSK_GPU_MODE_LOWLAT kernel has no IPv6 instance: a LOWLAT context with          */
-/* XSK_GPU_OPT_IPV6 set serves every batch through the launch path (same results, a launch per  */
-/* batch; xsk_gpu_ctx_mode() still reports LOWLAT).                                             */
+/* An XSK_GPU_MODE_LOWLAT context serves batches under XSK_GPU_OPT_IPV6 from its resident       */
+/* kernel like any other (a dual-stack instance of it: no launch, no sync).                     */
 /* ------------------------------------------------------------------------------------------ */
 #define XSK_GPU_OPT_IPV6 0x10u /* wire mode also answers ICMPv6 echo requests */
 #define XSK_GPU_OPT_MASK 0x17u /* every valid bit; 0x8 is reserved and rejected */
@@ -286,6 +285,12 @@ int xsk_gpu_init(xsk_gpu_ctx** out, int device, void* umem, uint64_t umem_size, 
 /* The mode `ctx` runs in (XSK_GPU_MODE_*): the one it was created with, except a LOWLAT request beyond
  * XSK_GPU_LOWLAT_PER_DEVICE, which runs as ZEROCOPY.  -EINVAL for NULL. */
 int xsk_gpu_ctx_mode(const xsk_gpu_ctx* ctx);
+
+/* Diagnostic hook (host-only; like the other xsk_gpu__ hooks not part of the ABI the version number covers): which
+ * path served the batches of a context that runs XSK_GPU_MODE_LOWLAT since init -- out[0] batches completed by the
+ * resident kernel, out[1] batches that took the launch path (above XSK_GPU_LOWLAT_MAX, a multi batch whose shares are
+ * launched, the untouched slices of a batch that timed out partly served).  -EINVAL for NULL or another mode. */
+int xsk_gpu__lowlat_served(const xsk_gpu_ctx* ctx, uint64_t out[2]);
 
 /* Synchronously process one batch of host descriptors against the bound UMEM.  Same outputs as
  * xsk_gpu_echo_dev(); `verdicts`, `recs` and `stats` are host pointers (each may be NULL).

@@ -7,10 +7,12 @@ in batches of 64 (RX_BATCH_SIZE, xsk_utils.h:8) up to 4096 frames, for the zeroc
 UMEM (untimed) so every call transforms echo requests.  Prints one JSON line per (frame length, mode, batch).
 
   python tools/hostlat.py [--lens 64,1500] [--modes zerocopy,staged,lowlat] [--batches 64,256,1024,4096] [--opts 7]
-                          [--gpus 0,0] [--reps 200] [--scramble]
+                          [--gpus 0,0] [--reps 200] [--scramble] [--v6]
 
 --scramble puts the descriptors in a random order over the UMEM's chunks: the RX ring of a client after its free stack
 (xsk_receive.c:55-71) has recycled frames in arbitrary order, so a batch's frames scatter over the 16 MiB.
+--v6 replays ICMPv6 echo requests of the same lengths (tests/golden/make_v6_golden.py's frame builder) at the same
+addresses; they are answered only with XSK_GPU_OPT_IPV6 in --opts (e.g. 23).  Every line carries the library's build id.
 """
 import argparse
 import itertools
@@ -25,6 +27,32 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import oracle  # noqa: E402  (frame generator only)
+
+
+def v6_requests(umem, descs, flen, seed=0x5EED0006):
+    """Overwrite every descriptor's frame with an untagged ICMPv6 echo request of flen bytes (>= 62): the builder of
+    tests/golden/make_v6_golden.py, each frame its own addresses, identifier and payload."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_v6_golden",
+                                                  os.path.join(ROOT, "tests", "golden", "make_v6_golden.py"))
+    G6 = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G6)
+    if flen < 62:
+        sys.exit("--v6 needs frame lengths >= 62 (Ethernet + IPv6 + ICMPv6 echo headers)")
+    rng = np.random.default_rng(seed)
+    for i, d in enumerate(descs):
+        f = G6.build6(saddr=bytes(rng.integers(0, 255, 16, dtype=np.uint8)),
+                      daddr=bytes(rng.integers(0, 255, 16, dtype=np.uint8)), ident=int(rng.integers(0, 65536)),
+                      seq=i & 0xFFFF, payload=bytes(rng.integers(0, 256, flen - 62, dtype=np.uint8)))
+        a = int(d["addr"])
+        umem[a:a + flen] = np.frombuffer(f, np.uint8)
+
+
+def build_id():
+    import ctypes
+    lib = ctypes.CDLL(os.path.join(ROOT, "xsknet_amd", "libxsknet_amd.so"))
+    lib.xsk_gpu_build_id.restype = ctypes.c_char_p
+    return lib.xsk_gpu_build_id().decode()
 
 
 def run_one(exe, p, flen, mode, batch, tile, args):
@@ -44,7 +72,7 @@ def run_one(exe, p, flen, mode, batch, tile, args):
         sys.exit(1)
     kv = dict(x.split("=") for x in r.stdout.split())
     us = float(kv["us_per_call"])
-    rec = {"frame_len": flen, "mode": mode, "batch": batch, "gpus": args.gpus or "0", "tile": tile or "auto", "groups": args.groups or "auto",
+    rec = {"build_id": args.build_id, "frames": "icmpv6" if args.v6 else "icmp", "frame_len": flen, "mode": mode, "batch": batch, "gpus": args.gpus or "0", "tile": tile or "auto", "groups": args.groups or "auto",
            "opts": args.opts, "umem_flushed": bool(args.flush), "umem_huge_pages": bool(args.huge), "scrambled": bool(args.scramble),
            "us_per_call": round(us, 2), "mframes_s": round(batch / us, 3), "calls": int(kv["calls"])}
     if "huge_kb" in kv:  # the UMEM's AnonHugePages: whether the kernel backed it with 2 MiB pages
@@ -75,7 +103,9 @@ def main():
     ap.add_argument("--groups", type=int, default=0, help="LOWLAT serving workgroups (echo_replay groups=; 0: by size)")
     ap.add_argument("--opts", type=int, default=0, help="wire-format options (echo_replay opts=; 7 = every option)")
     ap.add_argument("--scramble", action="store_true", help="descriptors in a random order over the UMEM's chunks")
+    ap.add_argument("--v6", action="store_true", help="replay ICMPv6 echo requests (answered with --opts 16..23)")
     args = ap.parse_args()
+    args.build_id = build_id()
     exe = os.path.join(ROOT, "tools", "echo_replay")
     n, chunk = 4096, 4096
     with tempfile.TemporaryDirectory() as td:
@@ -83,6 +113,8 @@ def main():
         for flen in (int(x) for x in args.lens.split(",")):
             umem = np.zeros(n * chunk, np.uint8)
             descs = oracle.synth_batch(umem, n, 256, chunk, seed=0x5EED0001, mode=0, len_lo=flen, len_hi=flen)
+            if args.v6:
+                v6_requests(umem, descs, flen)
             if args.scramble:
                 descs = np.ascontiguousarray(descs[np.random.default_rng(0x5C).permutation(n)])
             umem.tofile(p("u"))

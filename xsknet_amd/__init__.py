@@ -133,6 +133,7 @@ _SIGS = {
     "xsk_gpu__staged_stats": ([_P, C.POINTER(C.c_uint64)], C.c_int),
     "xsk_gpu__staged_noalias": ([_P, C.c_uint32], C.c_int),
     "xsk_gpu__lowlat_outcomes": ([_P, C.POINTER(C.c_uint64)], C.c_int),
+    "xsk_gpu__lowlat_served": ([_P, C.POINTER(C.c_uint64)], C.c_int),
     "xsk_gpu__lowlat_test_width": ([_P, C.c_uint32], C.c_int),
     "xsk_gpu__multi_ctx": ([_P, C.c_uint32], _P),
     "xsk_gpu__lowlat_live": ([C.c_int, C.POINTER(C.c_uint32)], C.c_int),
@@ -365,6 +366,12 @@ def staged_stats_of(ctx) -> dict:
     return dict(zip(STAGED_FIELDS, (int(x) for x in out)))
 
 
+def _lowlat_served_of(handle):
+    out = (C.c_uint64 * 2)()
+    _check("xsk_gpu__lowlat_served", lib().xsk_gpu__lowlat_served(handle, out))
+    return int(out[0]), int(out[1])
+
+
 class EchoContext:
     """Host-UMEM drop-in (xsk_gpu_init / xsk_gpu_process / xsk_gpu_fini) over a numpy uint8 UMEM."""
 
@@ -429,6 +436,11 @@ class EchoContext:
         out = (C.c_uint64 * 4)()
         _check("xsk_gpu__lowlat_outcomes", lib().xsk_gpu__lowlat_outcomes(self._ctx, out))
         return {"timeouts": int(out[0]), "partial": int(out[1]), "untouched": int(out[2]), "late": int(out[3])}
+
+    def lowlat_served(self):
+        """xsk_gpu__lowlat_served of a LOWLAT context: (batches completed by the resident kernel, batches that took
+        the launch path)."""
+        return _lowlat_served_of(self._ctx)
 
     def rx_step(self, rx: Ring, fill: Ring, tx: Ring, pool: FramePool, max_batch: int, stats=None):
         """xsk_gpu_rx_step on this context; returns (received, RxResult)."""
@@ -505,6 +517,11 @@ class MultiContext:
         """Test switch: every context forgets the UMEM's mapped alias (xsk_gpu__staged_noalias)."""
         for g in range(len(self.status())):
             _check("xsk_gpu__staged_noalias", lib().xsk_gpu__staged_noalias(self.context(g), half_bytes))
+
+    def lowlat_served(self):
+        """The member contexts' lowlat_served(), summed (every member runs LOWLAT)."""
+        per = [_lowlat_served_of(self.context(g)) for g in range(len(self.status()))]
+        return sum(a for a, _ in per), sum(b for _, b in per)
 
     def inject_failure(self, g: int, rc: int) -> None:
         """Test hook: context g's next share fails with rc (xsk_gpu__multi_inject)."""
@@ -589,6 +606,11 @@ class RxPipe:
         if not h:
             raise XskGpuError("xsk_gpu__rx_pipe_ctx", -22)
         return ContextView(h)
+
+    def lowlat_served(self):
+        """The pipe's contexts' lowlat_served(), summed (a LOWLAT pipe)."""
+        per = [self.context(i).lowlat_served() for i in range(self.depth)]
+        return sum(a for a, _ in per), sum(b for _, b in per)
 
     def close(self) -> None:
         if self._p:

@@ -86,6 +86,8 @@ struct xsk_gpu_ctx {
     uint64_t ll_outcome[4]; /* LOWLAT doorbell batches that missed their timeout: all, completed through the launch path
                              * after a partial service, returned -ETIMEDOUT, completed late (every slice served,
                              * found after STOP) -- xsk_gpu__lowlat_outcomes */
+    uint64_t ll_served[2];  /* LOWLAT batches completed by the resident kernel / that took the launch path (the
+                             * untouched slices of a partly served one among them) -- xsk_gpu__lowlat_served */
     /* the batch xsk_gpu__submit put in flight and xsk_gpu__complete has not taken back yet */
     uint32_t pend_n;      /* its frames; 0: none */
     int pend_bell;        /* on the doorbell (else launched) */
@@ -392,6 +394,12 @@ int xsk_gpu__lowlat_outcomes(const xsk_gpu_ctx* c, uint64_t out[4]) {
     for (int i = 0; i < 4; i++) out[i] = c->ll_outcome[i];
     return 0;
 }
+int xsk_gpu__lowlat_served(const xsk_gpu_ctx* c, uint64_t out[2]) {
+    if (!c || !out || !c->ll) return -EINVAL;
+    out[0] = c->ll_served[0];
+    out[1] = c->ll_served[1];
+    return 0;
+}
 xsk_gpu__lowlat* xsk_gpu__ctx_lowlat(xsk_gpu_ctx* c) { return c ? c->ll : NULL; }
 int xsk_gpu__umem_view(xsk_gpu_ctx* c, uint64_t off, void* out, uint64_t n) {
     if (!c || !out || !zerocopy(c) || off > c->umem_size || n > c->umem_size - off) return -EINVAL;
@@ -409,8 +417,9 @@ int xsk_gpu_set_options(xsk_gpu_ctx* c, uint32_t opts) {
     if (c->pend_n) return -EBUSY; /* the batch in flight runs under the options it was submitted with */
     if (c->ll) {
         (void)hipSetDevice(c->device);
-        /* (the resident kernel has no IPv6 instance: with XSK_GPU_OPT_IPV6 every batch is launched, xsk_gpu__submit) */
-        const int rc = xsk_gpu__lowlat_set_opts(c->ll, opts & XSK_GPU_OPT_ALL);
+        /* (a change stops the resident grid; the next batch starts the instance of the new word -- reference, wire or,
+         * with XSK_GPU_OPT_IPV6, dual-stack) */
+        const int rc = xsk_gpu__lowlat_set_opts(c->ll, opts);
         if (rc) return rc;
     }
     c->opts = opts;
@@ -602,8 +611,8 @@ int xsk_gpu__submit(xsk_gpu_ctx* c, const struct xsk_gpu_desc* descs, uint32_t n
          * until it has (-EBUSY), then the context is usable again */
         if (!xsk_gpu__lowlat_recover(c->ll)) return -EBUSY;
     }
-    /* the doorbell: no launch, no sync, no HIP call (never with XSK_GPU_OPT_IPV6: the resident kernel parses IPv4 only) */
-    if (c->ll && n <= XSK_GPU_LOWLAT_MAX && !no_doorbell && !(c->opts & XSK_GPU_OPT_IPV6)) {
+    /* the doorbell: no launch, no sync, no HIP call (under every option word: xsk_lowlat.hip has an instance for each) */
+    if (c->ll && n <= XSK_GPU_LOWLAT_MAX && !no_doorbell) {
         memcpy(xsk_gpu__lowlat_descs(c->ll), descs, (size_t)n * sizeof *descs);
         uint32_t w = 0;
         rc = xsk_gpu__lowlat_post(c->ll, n, want_recs, &w);
@@ -638,6 +647,7 @@ int xsk_gpu__submit(xsk_gpu_ctx* c, const struct xsk_gpu_desc* descs, uint32_t n
     c->pend_n = n;
     c->pend_bell = 0;
     c->pend_chunks = nchunks;
+    if (c->ll) c->ll_served[1]++;
     c->pend_recs = want_recs;
 out:
     if (caller_dev >= 0 && caller_dev != c->device) (void)hipSetDevice(caller_dev);
@@ -685,6 +695,7 @@ static int complete_doorbell(xsk_gpu_ctx* c, uint32_t n, uint8_t* verdicts, stru
             return rc;
         }
     }
+    if (!partial) c->ll_served[0]++; /* (a partly served one counted as launched: its untouched slices were) */
     if (verdicts) memcpy(verdicts, hv, n);
     if (stats) { /* xsk_receive.c:171-172, 229, 233 -- what the kernel's counter phase would add */
         uint64_t rxb = 0, txp = 0, txb = 0;

@@ -209,8 +209,7 @@ int xsk_gpu_multi_process(xsk_gpu_multi* m, const struct xsk_gpu_desc* descs, ui
      * every context runs LOWLAT (a LOWLAT request beyond the device's resident-kernel cap runs as ZEROCOPY) and every
      * share fits it; otherwise every context takes the launch path, and every resident kernel has stopped before
      * any share is launched, so no share runs beside a resident kernel that holds a CU */
-    /* (XSK_GPU_OPT_IPV6: the resident kernel has no IPv6 instance, so such contexts count as launched) */
-    m->job_launch = !m->all_lowlat || (m->opts & XSK_GPU_OPT_IPV6) || (n + m->G - 1) / m->G > XSK_GPU_LOWLAT_MAX;
+    m->job_launch = !m->all_lowlat || (n + m->G - 1) / m->G > XSK_GPU_LOWLAT_MAX;
     /* (with a downgraded context no batch ever takes a doorbell, so no resident kernel is ever started: nothing to
      * stop, per call or otherwise -- ADVICE r04) */
     if (m->job_launch && m->all_lowlat)

@@ -324,6 +324,104 @@ __global__ __launch_bounds__(kThreads6, 1) void lowlat_kernel(LowlatArgs L) {
     if (threadIdx.x == 0) atomicSub(&g_ll_live, 1u);
 }
 
+// The dual-stack instance (XSK_GPU_OPT_IPV6): lowlat_kernel<true>'s serving loop -- the same poll, acquire, completion
+// sequence and exits, statement for statement -- around the wire-mode body whose header phase also answers ICMPv6 echo
+// requests (wire_v6_phase; the one-tile form of echo_ds_kernel<true>).  A copy, not a shared inline function: with the
+// loop factored out the two kernels above came out with the same instructions in another order, and their streams are
+// pinned (tests/golden/kernel_isa.json).  A change to the loop above is a change here.
+__global__ __launch_bounds__(kThreads6, 1) void resident_ds_kernel(LowlatArgs L) {
+    __shared__ Echo6Smem<kLLTPW> sm;  // 64-B windows in both modes (wire: wire_header_phase64)
+    __shared__ uint32_t s_cmd[4];  // work?, n, recs | tile | dl, f0
+    // the body's phase stamps land in the LDS and go to the device-memory diagnostics after `done`: a store
+    // to host memory would put its PCIe acknowledgement in front of every later wait on a load (the
+    // vector memory counter retires in order) -- and a volatile one waits for its own
+    __shared__ unsigned long long s_trace[6];
+    xsk_gpu__bell* bell = L.bell;
+    const uint32_t g = blockIdx.x;
+    const bool leader = g == 0;
+    PollState P = {};  // wave 0: `served`, the two polls' registers, diagnostics
+    if (threadIdx.x == 0) atomicAdd(&g_ll_live, 1u);
+    if (threadIdx.x < 64) {  // wave 0 polls; every lane keeps the same `served`
+        // this workgroup's last completed batch (a previous instance's; stream order: it has exited)
+        P.served = uniform(ld_sys(&bell->wg[g].done));
+        if (leader) st_sys(&bell->wg[0].alive, 1u);
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    while (true) {
+        if (threadIdx.x < 64) {
+            if (leader) poll_doorbell<true>(L, sm.desc, s_cmd, P, g, lane);
+            else poll_doorbell<false>(L, sm.desc, s_cmd, P, g, lane);
+        }
+        // the command travels through the LDS only: an LDS-only barrier (__syncthreads() would first wait
+        // for wave 0's poll still in flight)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        const uint32_t work = s_cmd[0], n = s_cmd[1], recs = s_cmd[2] & 1u, tq = (s_cmd[2] >> 8) & 0xFFu;
+        const uint32_t dl = s_cmd[2] >> 16, f0 = s_cmd[3];
+        if (!work) break;  // workgroup-uniform
+        const uint64_t t_body = wall_clock64();
+        const uint64_t c_body = __builtin_amdgcn_s_memtime();
+        EchoArgs a;
+        a.umem = L.umem;
+        a.umem_size = L.umem_size;
+        a.descs = L.descs + f0;
+        a.n = n;
+        a.verdicts = L.verdicts + f0;
+        a.recs = recs ? L.recs + f0 : nullptr;
+        a.partials = nullptr;
+        a.opts = L.opts;
+        a.stats_direct = nullptr;  // the host counts from the descriptors and verdicts: no counter phase
+        a.trace = s_trace;
+        a.desc_in_lds = dl;
+        // spread the slice over all 16 waves: tiles of ceil(n / 16) frames (a multiple of 4: one 16-lane
+        // row per frame and step), so a 64-frame batch is 16 tiles of 4 frames, each wave one step
+        uint32_t tl = tq ? 4u * tq : ((n + kWaves6 - 1) / kWaves6 + 3u) & ~3u;
+        tl = tl < 4u ? 4u : (tl > (uint32_t)kTile ? (uint32_t)kTile : tl);
+        a.tile_live = tl;
+        const uint32_t ntiles = (n + tl - 1) / tl;
+        if (ntiles)
+            // wire mode on the reference form's 64-B windows and streams with wire_header_phase64 (the 128-B form took
+            // 11.6 us per 64 x 64-B call with every option against 8.7 in reference mode, profiles/r04/wll/)
+            echo6_body<kLLTPW, kLLSync, true, true, true, true, false, kRefHeavy, kU, false, false, 0, true, /*V6*/ true>(
+                a, 0u, ntiles, sm);
+        // the two polls' registers live across the body: a batch is taken while the other poll is still in
+        // flight, and registers the compiler reused would first have to wait for it to land
+        asm volatile("" ::"v"(P.cA), "v"(P.aA), "v"(P.bA), "v"(P.cB), "v"(P.aB), "v"(P.bB), "v"(P.yA), "v"(P.yB));
+        const uint64_t t_rel = wall_clock64();
+        const uint64_t c_rel = __builtin_amdgcn_s_memtime();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's stores have reached the L2 / fabric
+        __syncthreads();  // (also: sm.desc is rewritten by the next poll only after every wave is done)
+        if (threadIdx.x == 0) {
+            // system scope, once for the workgroup: write back the L2 lines of host memory the body wrote,
+            // wait for it, then publish completion (diagnostics after it: they are not waited for)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+            // the write-back must have completed before `done` leaves: ROCm 7.2 drops the fence's own
+            // `s_waitcnt vmcnt(0)` after buffer_wbl2 when this wave's scoreboard is provably empty (it is:
+            // the wait above), and `done` then overtook the verdicts (MI355X_MICROARCH.md, compiler hazard).
+            // tests/test_lowlat_isa.py checks this sequence in the built code object.
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint64_t t_end = wall_clock64();
+            __hip_atomic_store((uint32_t*)&bell->wg[g].done, P.served, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (leader) {  // plain stores to device memory: no wait here, acknowledged long before the next poll
+                xsk_gpu__lldiag* dg = L.diag;
+                dg->trace[0] = P.t_poll;
+                dg->trace[1] = t_body - P.t_seen;
+                dg->trace[2] = t_rel - t_body;
+                dg->trace[3] = t_end - t_rel;
+                for (int k = 0; k < 5; ++k) dg->body[k] = s_trace[k];
+                dg->body[5] = t_body;
+                dg->clk[0] = c_rel - c_body;
+                dg->clk[1] = t_rel - t_body;
+                dg->polls[0] = P.n_batches;
+                dg->polls[1] = P.n_polls;
+                dg->polls[2] = P.n_stale;
+            }
+        }
+    }
+    if (threadIdx.x == 0) atomicSub(&g_ll_live, 1u);
+}
+
+
 }  // namespace
 
 struct xsk_gpu__lowlat {
@@ -353,7 +451,9 @@ static int ll_launch(void* u) {
     if (c & XSK_GPU__BELL_STOP) xsk_gpu__ll_post(ll->h_bell, c & ~XSK_GPU__BELL_STOP);
     ll->args.gen++;
     const dim3 grid(ll->width ? ll->width : XSK_GPU__LL_WG);
-    if (ll->args.opts)
+    if (ll->args.opts & XSK_GPU_OPT_IPV6)
+        hipLaunchKernelGGL(resident_ds_kernel, grid, dim3(kThreads6), 0, ll->stream, ll->args);
+    else if (ll->args.opts)
         hipLaunchKernelGGL(lowlat_kernel<true>, grid, dim3(kThreads6), 0, ll->stream, ll->args);
     else
         hipLaunchKernelGGL(lowlat_kernel<false>, grid, dim3(kThreads6), 0, ll->stream, ll->args);
@@ -451,7 +551,7 @@ extern "C" void xsk_gpu__ll_yield_all(int delta) {
 }
 
 int xsk_gpu__lowlat_start(xsk_gpu__lowlat** out, void* d_umem, uint64_t umem_size, uint32_t opts) {
-    if (!out || !d_umem || (umem_size >> 48) || (opts & ~XSK_GPU_OPT_ALL)) return -EINVAL;
+    if (!out || !d_umem || (umem_size >> 48) || (opts & ~XSK_GPU_OPT_MASK)) return -EINVAL;
     *out = nullptr;
     xsk_gpu__lowlat* ll = (xsk_gpu__lowlat*)calloc(1, sizeof *ll);
     if (!ll) return -ENOMEM;
@@ -521,7 +621,7 @@ int xsk_gpu__lowlat_start(xsk_gpu__lowlat** out, void* d_umem, uint64_t umem_siz
 }
 
 int xsk_gpu__lowlat_set_opts(xsk_gpu__lowlat* ll, uint32_t opts) {
-    if (!ll || (opts & ~XSK_GPU_OPT_ALL)) return -EINVAL;
+    if (!ll || (opts & ~XSK_GPU_OPT_MASK)) return -EINVAL;
     if (opts == ll->args.opts) return 0;
     xsk_gpu__lowlat_stop(ll);  // the next batch launches the kernel of the new mode
     ll->args.opts = opts;
