@@ -214,6 +214,34 @@ int xsk_gpu_echo_dev_opts(void* d_umem, uint64_t umem_size, const struct xsk_gpu
                           uint32_t opts, uint8_t* d_verdicts, struct xsk_gpu_rec* d_recs,
                           struct xsk_gpu_stats* d_stats, void* d_workspace, void* stream);
 
+/* xsk_gpu_echo_dev_opts() with the frame count in device memory (build-added): the transform behind a producer that
+ * leaves its count on the device, such as xsk_gpu_classify_dev[_opts]() and its *d_nout.
+ *   d_n    : one uint32_t in device memory (4-B aligned).  The kernel reads n = min(*d_n, n_max) when it EXECUTES, not
+ *            when this call returns: the read is stream-ordered after whatever wrote *d_n earlier on `stream`.
+ *   n_max  : the bound the host knows, <= XSK_GPU_MAX_BATCH: d_descs, d_verdicts and d_recs hold n_max entries, and the
+ *            launches are sized for it.
+ * For i < n every UMEM byte, verdict, record and counter is exactly what xsk_gpu_echo_dev_opts(..., n, opts, ...)
+ * produces.  d_verdicts[i] and d_recs[i] for n <= i < n_max are not written, and no frame of a descriptor at an index
+ * >= n is read or written (nor is the descriptor).  *d_n == 0 changes nothing.
+ * d_stats is one xsk_gpu_stats in device memory, accumulated with device-scope atomics as by xsk_gpu_echo_dev(), or
+ * NULL.  There is no workspace argument: the per-workgroup partial rows exist only for counters in mapped host memory,
+ * a path this entry point does not have.
+ * Every argument is checked before any device call: d_n NULL or not 4-B aligned, n_max > XSK_GPU_MAX_BATCH, option
+ * bits outside XSK_GPU_OPT_MASK, and the pointer and alignment rules of xsk_gpu_echo_dev_opts() are -EINVAL;
+ * n_max == 0 returns 0 without a launch.
+ * The call allocates nothing, synchronises nothing and reads no device memory from the host, so a stream under graph
+ * capture may contain it, and a replay serves whatever *d_n holds then.  The bench timer (xsk_gpu_timing_enable) does
+ * not bracket it.
+ * Kernels: the 64-frame-tile round kernel of the option word (reference, wire, dual stack).  One workgroup per compute
+ * unit, at most one per tile of n_max, is launched; each reads the count and takes the share the direct launch of n
+ * frames would give it, or leaves at once.  A bound of more than 4 rounds per workgroup runs as consecutive launches,
+ * as the direct call's does.  A small n_max runs on the same kernel: the sub-tile kernels that
+ * xsk_gpu_echo_dev_opts() picks for n <= XSK_GPU_LOWLAT_MAX have no indirect form, so for a small batch whose count the
+ * host knows the direct call is the faster one. */
+int xsk_gpu_echo_dev_indirect(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs,
+                              const uint32_t* d_n, uint32_t n_max, uint32_t opts, uint8_t* d_verdicts,
+                              struct xsk_gpu_rec* d_recs, struct xsk_gpu_stats* d_stats, void* stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Host-UMEM entry points: the drop-in for the client's RX loop (xsk_receive.c:192-237).       */
 /* ------------------------------------------------------------------------------------------ */
@@ -421,6 +449,31 @@ int xsk_gpu_classify_dev(const void* d_umem, uint64_t umem_size, const struct xs
 int xsk_gpu_classify_dev_opts(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
                               uint32_t opts, int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out,
                               uint32_t* d_nout, void* d_workspace, void* stream);
+
+/* Ingress on the device in one asynchronous call (build-added): xsk_gpu_classify_dev_opts(..., d_out, d_nout, ...)
+ * followed on the same stream by xsk_gpu_echo_dev_indirect(d_umem, umem_size, d_out, d_nout, n, opts, ...).  The count
+ * of redirected frames never comes to the host, so the call needs no synchronisation and can be captured in a graph.
+ *   d_actions            : n bytes, the filter's actions, by batch position
+ *   d_out, d_nout        : required (d_out 16-B aligned, room for n descriptors; d_nout 4-B aligned): the REDIRECT
+ *                          descriptors in batch order and their count
+ *   d_verdicts, d_recs   : n entries each (or NULL), indexed by position in d_out; entries at or above *d_nout are not
+ *                          written
+ *   d_stats              : device memory, accumulated, or NULL
+ *   d_workspace          : xsk_gpu_classify_workspace_size(n) bytes
+ * opts == 0 pairs the reference's filter (xsk_gpu_classify_dev) with the reference transform (xsk_gpu_echo_dev);
+ * nonzero opts pair the filter and the transform of that option word.  target_bound == 0 gives *d_nout = 0, and no
+ * frame or counter changes.  n == 0 writes *d_nout = 0, as the filter does.  All arguments are checked before the
+ * first launch (the rules of both calls; -EINVAL).
+ * The counters behind the filter: rx_packets grows by *d_nout and rx_bytes by the sum of the redirected frames' len.
+ * For nonzero opts the tx counters and every UMEM byte equal what xsk_gpu_echo_dev_opts() alone leaves over the whole
+ * batch: every frame the transform would answer is REDIRECT, and only an answered frame is rewritten or counted as
+ * transmitted.  For opts == 0 that does NOT hold: the reference's filter drops every frame of len < 34, while the
+ * reference transform answers some frames of 20 to 33 bytes (it reads bytes up to 38 wherever the UMEM holds them);
+ * behind the filter those frames stay as they are, as they do behind the reference's XDP program. */
+int xsk_gpu_ingress_dev_opts(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
+                             uint32_t opts, int target_bound, uint8_t* d_actions, struct xsk_gpu_desc* d_out,
+                             uint32_t* d_nout, uint8_t* d_verdicts, struct xsk_gpu_rec* d_recs,
+                             struct xsk_gpu_stats* d_stats, void* d_workspace, void* stream);
 
 /* The UMEM allocation for the host modes: the reference allocates its UMEM with posix_memalign(getpagesize(),
  * NUM_FRAMES * FRAME_SIZE) (src/lib/xsk_utils.c:132-135); this gives the same kind of memory (anonymous, private,

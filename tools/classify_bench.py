@@ -15,12 +15,24 @@ written per redirected frame.
 (VLAN stacks, IPv4 and IPv6, truncations) tiled to 1 M frames at the same 2048-B stride.  The echo leg is not re-armed
 then (xsk_gpu_rearm_dev restores IPv4 replies only): after the first repetition most echo requests have become
 replies, so with --traffic dual only the classify figures are comparable between runs.
+
+--ingress runs two interleaved A/B comparisons instead, five runs a leg, and appends their JSON lines to
+--out DIR/pipeline.jsonl and DIR/indirect.jsonl (profiles/ingress/):
+  (a) filter -> transform on the synthetic 1 M slab: classify_dev, the count copied to the host behind a
+      synchronisation, echo_dev with that count (leg "roundtrip") against one ingress_dev call (leg "ingress").  Host
+      clock from before the first enqueue to the return of the final synchronisation, which both legs end in;
+  (b) the transform alone on c3's shape (1 M x 1500 B at a 4 KiB stride): echo_dev(n) (leg "direct") against
+      echo_dev_indirect with *d_n == n_max == n (leg "indirect"), device events.
+Frames are re-armed between repetitions, untimed.  The last line of each file gives the medians, the spread (max - min)
+of each leg's five runs and the ratio of the medians; the baseline is the first leg.
 """
 import argparse
 import ctypes as C
 import json
 import os
+import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,14 +42,131 @@ import torch  # noqa: E402
 import xsknet_amd as X  # noqa: E402
 
 
+def _summarise(path, what, legs, runs, extra):
+    """Append the runs of an A/B (legs[0] is the baseline) and their summary line to `path`."""
+    med = {leg: statistics.median(runs[leg]) for leg in legs}
+    line = {"cmp": what, "summary": True, **extra}
+    for leg in legs:
+        line[f"{leg}_us_median"] = round(med[leg], 2)
+        line[f"{leg}_us_spread"] = round(max(runs[leg]) - min(runs[leg]), 2)
+    line["ratio"] = round(med[legs[1]] / med[legs[0]], 4)
+    line["delta_us"] = round(med[legs[1]] - med[legs[0]], 2)
+    line["within_baseline_spread"] = bool(med[legs[1]] - med[legs[0]] <= max(runs[legs[0]]) - min(runs[legs[0]]))
+    with open(path, "a") as f:
+        for i in range(len(runs[legs[0]])):
+            for leg in legs:
+                f.write(json.dumps({"cmp": what, "leg": leg, "run": i, "us": round(runs[leg][i], 2), **extra}) + "\n")
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line))
+
+
+def ingress_compare(args):
+    n, reps, nruns = 1 << 20, 10, 5
+    dev = torch.device("cuda:0")
+    os.makedirs(args.out, exist_ok=True)
+    # ---- (a) filter -> transform, with and without the host round trip ----
+    stride = 2048
+    umem = torch.zeros(n * stride, dtype=torch.uint8, device=dev)
+    descs = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    X.synth_dev(umem, descs, n, 0, stride, 0x5EED0E0E, 0, 1, 1, 20, 1500)  # mixed traffic
+    act = torch.empty(n, dtype=torch.uint8, device=dev)
+    red = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+    nred = torch.zeros(1, dtype=torch.int32, device=dev)
+    verd = torch.empty(n, dtype=torch.uint8, device=dev)
+    stats = torch.zeros(40, dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(X.lib().xsk_gpu_classify_workspace_size(n)), dtype=torch.uint8, device=dev)
+    ews = torch.zeros(X.workspace_size(0, n), dtype=torch.uint8, device=dev)
+    redirected = []
+
+    def roundtrip():
+        X.classify_dev(umem, descs, n, True, act, red, nred, ws, opts=args.opts)
+        torch.cuda.synchronize()
+        k = int(nred.cpu()[0])
+        X.echo_dev(umem, red, k, verd, None, stats, ews, opts=args.opts)
+        return k
+
+    def ingress():
+        X.ingress_dev(umem, descs, n, True, act, red, nred, verd, None, stats, ws, opts=args.opts)
+        return None
+
+    def run_a(leg):
+        tot = 0.0
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            k = leg()
+            torch.cuda.synchronize()
+            tot += time.perf_counter() - t0
+            k = int(nred.cpu()[0]) if k is None else k
+            redirected.append(k)
+            X.rearm_dev(umem, red, verd, k)
+        return tot / reps * 1e6
+
+    legs = {"roundtrip": roundtrip, "ingress": ingress}
+    for leg in legs.values():  # warm-up of every kernel either leg launches
+        run_a(leg)
+    runs = {name: [] for name in legs}
+    for _ in range(nruns):
+        for name, leg in legs.items():
+            runs[name].append(run_a(leg))
+    assert len(set(redirected)) == 1, set(redirected)  # re-armed: every repetition filters the same traffic
+    _summarise(os.path.join(args.out, "pipeline.jsonl"), "filter_then_transform", list(legs), runs,
+               {"frames": n, "redirected": redirected[0], "opts": args.opts, "clock": "host, ends in a synchronise",
+                "reps_per_run": reps})
+    del umem, descs, act, red, verd
+    torch.cuda.empty_cache()
+    # ---- (b) the transform alone on c3's shape: host count against device count ----
+    stride = 4096
+    umem = torch.zeros(n * stride, dtype=torch.uint8, device=dev)
+    descs = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    X.synth_dev(umem, descs, n, 0, stride, 0x5EED0003, 0, 1, 0, 1500, 1500)
+    verd = torch.empty(n, dtype=torch.uint8, device=dev)
+    cnt = torch.full((1,), n, dtype=torch.int32, device=dev)
+
+    def direct():
+        X.echo_dev(umem, descs, n, verd, None, stats, ews)
+
+    def indirect():
+        X.echo_dev_indirect(umem, descs, cnt, n, verd, None, stats)
+
+    def run_b(leg):
+        tot = 0.0
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            leg()
+            e1.record()
+            X.rearm_dev(umem, descs, verd, n)
+            torch.cuda.synchronize()
+            tot += e0.elapsed_time(e1)
+        return tot / reps * 1e3
+
+    legs = {"direct": direct, "indirect": indirect}
+    for leg in legs.values():
+        run_b(leg)
+    runs = {name: [] for name in legs}
+    for _ in range(nruns):
+        for name, leg in legs.items():
+            runs[name].append(run_b(leg))
+    _summarise(os.path.join(args.out, "indirect.jsonl"), "transform_c3", list(legs), runs,
+               {"frames": n, "frame_len": 1500, "stride": stride, "opts": 0, "clock": "device events",
+                "reps_per_run": reps})
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ingress", action="store_true", help="the two A/B comparisons of DESIGN.md 9.2 instead")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ingress"), help="--ingress: where the lines go")
     ap.add_argument("--lib", default="")
     ap.add_argument("--opts", type=lambda x: int(x, 0), default=0, help="XSK_GPU_OPT_* word for the filter and the echo")
     ap.add_argument("--traffic", choices=["synth", "dual"], default="synth")
     args = ap.parse_args()
     if args.lib and args.opts:
         ap.error("--lib times xsk_gpu_classify_dev of another build: it takes no option word")
+    if args.ingress:
+        if args.lib or args.traffic != "synth":
+            ap.error("--ingress compares this build's entry points on the synthetic slab")
+        return ingress_compare(args)
     n, stride, reps = 1 << 20, 2048, 20
     dev = torch.device("cuda:0")
 

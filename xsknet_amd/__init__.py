@@ -101,6 +101,9 @@ _SIGS = {
     "xsk_gpu_workspace_size": ([C.c_int, C.c_uint32], C.c_size_t),
     "xsk_gpu_echo_dev": ([_P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_echo_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_echo_dev_indirect": ([_P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_ingress_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P],
+                                 C.c_int),
     "xsk_gpu_set_options": ([_P, C.c_uint32], C.c_int),
     "xsk_gpu_init": ([C.POINTER(_P), C.c_int, _P, C.c_uint64, C.c_uint32, C.c_int], C.c_int),
     "xsk_gpu_process": ([_P, _P, C.c_uint32, _P, _P, _P], C.c_int),
@@ -237,6 +240,15 @@ def echo_dev(umem, descs, n: int, verdicts=None, recs=None, stats=None, workspac
         _ptr(workspace), _stream_ptr(stream)))
 
 
+def echo_dev_indirect(umem, descs, count, n_max: int, verdicts=None, recs=None, stats=None, stream=None,
+                      opts: int = 0) -> None:
+    """xsk_gpu_echo_dev_indirect: the transform over the first min(count[0], n_max) descriptors, where `count` is a
+    uint32 word on the device (an int32 tensor of one element) that the kernel reads when it executes."""
+    _check("xsk_gpu_echo_dev_indirect", lib().xsk_gpu_echo_dev_indirect(
+        _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), _ptr(count), n_max, opts, _ptr(verdicts),
+        _ptr(recs), _ptr(stats), _stream_ptr(stream)))
+
+
 XDP_DROP, XDP_PASS, XDP_REDIRECT = 1, 2, 4
 
 
@@ -256,6 +268,20 @@ def classify_dev(umem, descs, n: int, bound: bool, actions, out=None, nout=None,
     _check("xsk_gpu_classify_dev", lib().xsk_gpu_classify_dev(
         _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, 1 if bound else 0, _ptr(actions), _ptr(out),
         _ptr(nout), _ptr(workspace), _stream_ptr(stream)))
+
+
+def ingress_dev(umem, descs, n: int, bound: bool, actions, out, nout, verdicts=None, recs=None, stats=None,
+                workspace=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_ingress_dev_opts: classify_dev(opts) and, on the same stream, echo_dev_indirect(opts) over its
+    compacted descriptors `out` and their count `nout`, with no host synchronisation between them.  Inside a graph
+    capture pass `workspace` (classify_workspace_size bytes): allocating it here would be part of the capture."""
+    if workspace is None:
+        import torch
+        workspace = torch.empty(int(lib().xsk_gpu_classify_workspace_size(max(n, 1))), dtype=torch.uint8,
+                                device=umem.device)
+    _check("xsk_gpu_ingress_dev_opts", lib().xsk_gpu_ingress_dev_opts(
+        _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, opts, 1 if bound else 0, _ptr(actions),
+        _ptr(out), _ptr(nout), _ptr(verdicts), _ptr(recs), _ptr(stats), _ptr(workspace), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,

@@ -69,6 +69,11 @@ XSK_GPU__HIDDEN int xsk_gpu__stage_unpack_dev(const void* d_stage, const uint32_
 XSK_GPU__HIDDEN void xsk_gpu__echo_ds_launch(const void* args, uint32_t grid, uint32_t tiles_per_wg, int small,
                                              void* stream);
 
+/* xsk_echo_ds_indirect.hip: launch the dual-stack kernel of xsk_gpu_echo_dev_indirect() for the piece [i0, i0 + len) of
+ * a batch whose count is *d_n (xsk_echo_indirect.hip); the launch's outcome is left in hipGetLastError(). */
+XSK_GPU__HIDDEN void xsk_gpu__echo_ds_indirect_launch(const void* args, const uint32_t* d_n, uint32_t i0, uint32_t len,
+                                                      uint32_t grid, void* stream);
+
 /* xsk_echo.hip: xsk_gpu_echo_dev_opts for counters in mapped host memory (no device atomics): d_stats
  * must be a slot zeroed for this call (a one-workgroup launch stores the counters without reading it).
  * tile: frames per wave of a small batch (xsk_gpu__small_tile), 0 = ceil(n / 16). */
