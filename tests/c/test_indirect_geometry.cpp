@@ -1,8 +1,10 @@
-// The launch geometry of xsk_gpu_echo_dev_indirect (xsknet_amd/csrc/xsk_echo_indirect.h) compiled for the host: for
-// launches sized from a bound n_max, and every count n <= n_max the kernels may read, the shares the workgroups of all
-// pieces work out for themselves partition the tiles of n -- none twice, none missing -- and within one launch each
-// workgroup's share is the one the direct launch of that many frames gives it (echo6_geometry, transcribed below from
-// xsknet_amd/csrc/xsk_echo_device.h, which is device code).  Stand-alone: prints "indirect geometry ok".
+// The transform's launch geometry (xsknet_amd/csrc/xsk_echo_geometry.h) and the device prologue of
+// xsk_gpu_echo_dev_indirect (xsk_echo_indirect.h) compiled for the host: for launches sized from a bound n_max, and
+// every count n <= n_max the kernels may read, the shares the workgroups of all pieces work out for themselves
+// partition the tiles of n -- none twice, none missing -- and within one launch each workgroup's share is the one the
+// direct launch of that many frames gives it (echo6_geometry, the function the host launches with).  Then the small
+// batches' sub-tiling (echo6_small_tiling), for every size the host may give it.  Stand-alone: prints "indirect
+// geometry ok".
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,16 +14,6 @@
 #include "../../xsknet_amd/csrc/xsk_echo_indirect.h"
 
 using namespace xskgpu;
-
-static void direct_geometry(uint32_t n, uint32_t num_cu, uint32_t* grid, uint32_t* tiles_per_wg) {
-    const uint32_t ntiles = (n + 64 - 1) / 64;
-    uint32_t g = num_cu < 1 ? 1 : num_cu;
-    if (g > ntiles) g = ntiles < 1 ? 1 : ntiles;
-    const uint32_t per = (ntiles + g - 1) / g;
-    *tiles_per_wg = per < 1 ? 1 : per;
-    *grid = (ntiles + *tiles_per_wg - 1) / *tiles_per_wg;
-    if (*grid < 1) *grid = 1;
-}
 
 #define CHECK(c, ...)                     \
     do {                                  \
@@ -43,7 +35,7 @@ static uint32_t rnd(uint32_t bound) {  // xorshift64*, [0, bound]
 static uint64_t check_one(uint32_t n_max, uint32_t ncu, uint32_t n, std::vector<uint8_t>& seen) {
     const uint32_t ntiles_max = ind_ntiles(n_max), ntiles = ind_ntiles(n);
     uint32_t piece_tiles = 0;
-    const uint32_t pieces = ind_pieces(n_max, ncu, &piece_tiles);
+    const uint32_t pieces = echo6_pieces(n_max, ncu, &piece_tiles);
     CHECK(piece_tiles >= 1 && (uint64_t)pieces * piece_tiles >= ntiles_max, "pieces do not cover n_max %u", n_max);
     seen.assign(ntiles_max + 1, 0);
     uint64_t shares = 0;
@@ -53,12 +45,12 @@ static uint64_t check_one(uint32_t n_max, uint32_t ncu, uint32_t n, std::vector<
         const uint64_t cap = (uint64_t)piece_tiles * 64;
         const uint32_t len = (uint32_t)(n_max - i0 < cap ? n_max - i0 : cap);
         sum_len += len;
-        const uint32_t grid = ind_grid(len, ncu);
+        const uint32_t grid = echo6_max_grid(len, ncu);
         CHECK(grid >= 1 && grid <= ncu && grid <= ind_ntiles(len), "grid %u for len %u ncu %u", grid, len, ncu);
         const uint32_t np = ind_piece_n(n, i0, len);  // the kernel's prologue
         CHECK(np <= len && (n <= i0 ? np == 0 : np == (n - i0 < len ? n - i0 : len)), "piece_n");
         uint32_t dg = 0, dper = 0;
-        direct_geometry(np, ncu, &dg, &dper);
+        echo6_geometry(np, ncu, &dg, &dper);
         const uint32_t nt = ind_ntiles(np);
         for (uint32_t wg = 0; wg < grid; ++wg) {
             uint32_t b = 0, e = 0;
@@ -87,6 +79,29 @@ static uint64_t check_one(uint32_t n_max, uint32_t ncu, uint32_t n, std::vector<
     return shares;
 }
 
+// A small batch's sub-tiles (echo_launch: n <= XSK_GPU_LOWLAT_MAX; `tile` 0 or the zerocopy context's, grid_force 0 or
+// the tests' and tools' workgroup count): live frames per tile a multiple of 4 in [4, 64], the launch covers the batch,
+// every workgroup has a tile, and an unforced grid's partial rows fit the workspace the caller was told to bring.
+static void check_small_tiling(void) {
+    const uint32_t tiles[] = {0, 4, 8, 64}, forces[] = {0, 1, 3, 16};
+    for (uint32_t n = 1; n <= 1024; ++n)
+        for (uint32_t tile : tiles)
+            for (uint32_t gf : forces) {
+                uint32_t tl = 0, per = 0, grid = 0;
+                echo6_small_tiling(n, tile, gf, &tl, &per, &grid);
+                CHECK(tl >= 4 && tl <= 64 && tl % 4 == 0, "n %u tile %u force %u: tl %u", n, tile, gf, tl);
+                CHECK((uint64_t)grid * per * tl >= n, "n %u tile %u force %u: %u x %u x %u frames", n, tile, gf, grid,
+                      per, tl);
+                const uint32_t nt = (n + tl - 1) / tl;
+                CHECK(grid >= 1 && per >= 1 && (uint64_t)(grid - 1) * per < nt,
+                      "n %u tile %u force %u: workgroup %u of %u x %u tiles has none of %u", n, tile, gf, grid - 1, grid,
+                      per, nt);
+                if (gf == 0)
+                    CHECK(grid <= echo6_workspace_rows(n), "n %u tile %u: %u workgroups, %u workspace rows", n, tile,
+                          grid, echo6_workspace_rows(n));
+            }
+}
+
 int main(void) {
     const uint32_t n_maxes[] = {1, 64, 65, 1024, 1025, 16385, (1u << 21) + 64};
     const uint32_t ncus[] = {1, 16, 256};
@@ -109,9 +124,10 @@ int main(void) {
     // the piece rule by hand: 256 CUs, 128 tiles (4 rounds) per workgroup is one launch, one tile more is
     // 5 rounds -> ceil(5 / 2) = 3 launches
     uint32_t pt = 0;
-    CHECK(ind_pieces(1u << 21, 256, &pt) == 1 && pt == 32768, "2^21 frames on 256 CUs: one launch");
-    CHECK(ind_pieces((1u << 21) + 64, 256, &pt) == 3 && pt == 10923, "2^21 + 64 frames on 256 CUs: three launches");
-    CHECK(ind_grid(0xFFFFFF00u, 256) == 256 && ind_ntiles(0xFFFFFF00u) == 0x3FFFFFCu, "XSK_GPU_MAX_BATCH");
+    CHECK(echo6_pieces(1u << 21, 256, &pt) == 1 && pt == 32768, "2^21 frames on 256 CUs: one launch");
+    CHECK(echo6_pieces((1u << 21) + 64, 256, &pt) == 3 && pt == 10923, "2^21 + 64 frames on 256 CUs: three launches");
+    CHECK(echo6_max_grid(0xFFFFFF00u, 256) == 256 && ind_ntiles(0xFFFFFF00u) == 0x3FFFFFCu, "XSK_GPU_MAX_BATCH");
+    check_small_tiling();
     printf("indirect geometry ok: %llu cases, %llu shares\n", (unsigned long long)cases, (unsigned long long)shares);
     return 0;
 }

@@ -90,8 +90,9 @@ def test_ingress_argument_validation_needs_no_gpu():
 
 
 def test_indirect_geometry_partitions_the_tiles_and_equals_the_direct_shares():
-    """xsk_echo_indirect.h on the host: n_max in {1, 64, 65, 1024, 1025, 16385, 2^21 + 64} x ncu in {1, 16, 256}, every
-    n in {0, 1, 63, 64, 65, n_max - 1, n_max} and 1000 random ones each."""
+    """xsk_echo_geometry.h and xsk_echo_indirect.h on the host: n_max in {1, 64, 65, 1024, 1025, 16385, 2^21 + 64} x ncu
+    in {1, 16, 256}, every n in {0, 1, 63, 64, 65, n_max - 1, n_max} and 1000 random ones each; then the small batches'
+    sub-tiling for every n in 1..1024, tile in {0, 4, 8, 64} and forced grid in {0, 1, 3, 16}."""
     with tempfile.TemporaryDirectory() as td:
         exe = os.path.join(td, "t")
         subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-o", exe,

@@ -2,10 +2,12 @@
 
 The gfx950 code objects of xsknet_amd/libxsknet_amd.so (its .hip_fatbin offload bundles) are disassembled with
 llvm-objdump; each kernel's instruction text (the encodings and address comments dropped: branch offsets are relative)
-is hashed.  tests/golden/kernel_isa.json pins the transform kernels -- echo_round_kernel (launched, reference and wire
-mode, large and small batches) and lowlat_kernel (the resident doorbell kernel, both modes) -- so that a source change
-meant to leave them alone (pruning dead switches from xsk_echo_device.h) is checked to be
-byte-identical in the built code, and a change meant to alter them updates the manifest deliberately:
+is hashed.  tests/golden/kernel_isa.json pins the twelve transform kernels, every instance of echo6_body --
+echo_round_kernel (launched, reference and wire mode, large and small batches), lowlat_kernel (the resident doorbell
+kernel, both modes), their dual-stack forms echo_ds_kernel and resident_ds_kernel, and the indirect-count kernels
+echo_indirect_kernel and echo_ds_indirect_kernel -- so that a source change meant to leave them alone (pruning dead
+switches from xsk_echo_device.h; naming the body's switches) is checked to be byte-identical in
+the built code, and a change meant to alter them updates the manifest deliberately:
 
     python tools/isa_manifest.py            # print every kernel's hash
     python tools/isa_manifest.py --check    # compare the pinned kernels with tests/golden/kernel_isa.json
@@ -24,7 +26,8 @@ sys.path.insert(0, ROOT)
 from tests.test_lowlat_isa import LIB, LLVM, gfx950_code_objects  # noqa: E402
 
 MANIFEST = os.path.join(ROOT, "tests", "golden", "kernel_isa.json")
-PINNED = re.compile(r"echo_round_kernel|lowlat_kernel")
+PINNED = re.compile(r"echo_round_kernel|lowlat_kernel|echo_ds_kernel|resident_ds_kernel|echo_indirect_kernel|"
+                    r"echo_ds_indirect_kernel")
 
 
 def kernel_hashes(lib=LIB):

@@ -56,17 +56,16 @@ __global__ __launch_bounds__(kThreads6, 1) void timed_round_kernel(EchoArgs a, u
     __shared__ Echo6Smem<kRefTPW> sm;
     const uint64_t t0 = wall_clock64();
     const uint32_t ntiles = (a.n + kTile - 1) / kTile;
-    constexpr uint32_t kRound = (uint32_t)kWaves6 * kRefTPW;
     if (PERM == 2) {
         for (uint32_t k = 0;; ++k) {
-            const uint32_t tb = (k * gridDim.x + blockIdx.x) * kRound;
+            const uint32_t tb = (k * gridDim.x + blockIdx.x) * kRoundTiles;
             if (tb >= ntiles) break;
-            echo6_body<kRefTPW, 2, false, false, false, false, true, kRefHeavy, kUR, true, true, kRefSlack, true>(a, tb, min(ntiles, tb + kRound), sm);
+            echo6_body<RoundCfg<false, false>>(a, tb, min(ntiles, tb + kRoundTiles), sm);
         }
     } else {
         const uint32_t g = (PERM == 1 && (blockIdx.x ^ 1u) < gridDim.x) ? blockIdx.x ^ 1u : blockIdx.x;
         const uint32_t t_begin = g * per, t_end = min(ntiles, t_begin + per);
-        echo6_body<kRefTPW, 2, false, false, false, false, true, kRefHeavy, kUR, true, true, kRefSlack, true>(a, t_begin, t_end, sm);
+        echo6_body<RoundCfg<false, false>>(a, t_begin, t_end, sm);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -90,12 +89,7 @@ extern "C" int xsk_gpu__product_variant(int variant, uint32_t grid_force, void* 
     uint32_t grid = 0, per = 0;
     echo6_geometry(n, grid_force ? grid_force : xsk_gpu__num_cu(device), &grid, &per);
     EchoArgs args;
-    args.umem = (uint8_t*)d_umem;
-    args.umem_size = umem_size;
-    args.descs = d_descs;
-    args.n = n;
-    args.verdicts = d_verdicts;
-    args.recs = d_recs;
+    if (!echo_args_init(&args, d_umem, umem_size, d_descs, n, 0, d_verdicts, d_recs)) return -EINVAL;
     args.partials = (unsigned long long*)d_workspace;  // counters as per-workgroup partial rows
     const hipStream_t s = (hipStream_t)stream;
     const dim3 gg(grid), bb(kThreads6);

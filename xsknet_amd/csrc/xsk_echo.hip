@@ -46,8 +46,6 @@ __global__ __launch_bounds__(1024) void fold_counters_kernel(const unsigned long
 
 thread_local const char* g_last_error = "ok";
 
-constexpr uint32_t kSmallWG = 16;  // workgroups a small batch's sub-tiles may spread over
-
 // ---- kernel timing (bench instrumentation) -------------------------------------------------------
 // Events are created per device, lazily, on the device of the launch they bracket; a slot is claimed
 // only once its start event has been recorded.
@@ -118,12 +116,7 @@ const char* xsk_gpu_last_error(void) { return g_last_error; }
 
 size_t xsk_gpu_workspace_size(int device, uint32_t n) {
     if (device < 0) return 0;
-    // room for the partial rows of the round kernel's grid (<= one workgroup per CU), or of a small batch's
-    // sub-tiles (<= kSmallWG workgroups)
-    const uint32_t ntiles = (n + kTile - 1) / kTile;
-    uint32_t g = ntiles < kMaxCuBound ? ntiles : kMaxCuBound;
-    if (g < kSmallWG) g = kSmallWG;
-    return (size_t)g * 4 * sizeof(unsigned long long);
+    return (size_t)echo6_workspace_rows(n) * 4 * sizeof(unsigned long long);
 }
 
 // Compute units of `device` (cached, race-free: concurrent first lookups store the same value).
@@ -146,14 +139,10 @@ uint32_t xsk_gpu__num_cu(int device) {
 static int echo_launch(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n, uint32_t opts,
                        uint8_t* d_verdicts, struct xsk_gpu_rec* d_recs, struct xsk_gpu_stats* d_stats,
                        void* d_workspace, void* stream, int hoststats, uint32_t tile, uint32_t grid_force = 0) {
-    if (opts & ~XSK_GPU_OPT_MASK) return -EINVAL;  // (0x8 is reserved)
-    if (n == 0) return 0;
-    if (n > XSK_GPU_MAX_BATCH) return -EINVAL;
-    if (!d_umem || !d_descs || ((uintptr_t)d_umem & 15u) || (umem_size & 15u) || ((uintptr_t)d_descs & 15u) ||
-        ((uintptr_t)d_recs & 15u))
-        return -EINVAL;
+    if (n == 0) return (opts & ~XSK_GPU_OPT_MASK) ? -EINVAL : 0;  // (an empty batch: only the options are checked)
+    EchoArgs args;
+    if (!echo_args_init(&args, d_umem, umem_size, d_descs, n, opts, d_verdicts, d_recs)) return -EINVAL;
     if (d_stats && !d_workspace) return -EINVAL;
-    if (umem_size >> 48) return -EINVAL;  // FrameMeta6 carries 48-bit UMEM offsets (both modes)
     int device = 0;
     HIP_TRY(hipGetDevice(&device));
     const uint32_t ncu = xsk_gpu__num_cu(device);
@@ -163,32 +152,11 @@ static int echo_launch(void* d_umem, uint64_t umem_size, const struct xsk_gpu_de
     // (zerocopy host UMEM) one wave alone would stream its 64 frames with only its own loads in flight, and in
     // HBM a 64-frame tile per CU leaves the batch's latency to one wave
     const bool small = n <= (uint32_t)XSK_GPU_LOWLAT_MAX;
+    const uint32_t wgs = grid_force ? grid_force : ncu;  // workgroups a large batch may use
     uint32_t tl = kTile;
-    if (small) {
-        // sub-tiles of tl frames, one per wave, over up to kSmallWG workgroups of 16 waves: a device-resident
-        // batch on every one of them (tl = ceil(n / 256), >= 4: tools/smallbatch.py measured 1024 x 1500 B in
-        // 14.6 us over 16 workgroups against 44.1 us on one); a zerocopy batch with the caller's tile (about
-        // 8 KiB of PCIe reads per wave, xsk_gpu__small_tile_w), 16 waves per workgroup
-        tl = tile ? ((tile + 3u) & ~3u)
-                  : ((n + kWaves6 * (grid_force ? grid_force : kSmallWG) - 1) /
-                         (kWaves6 * (grid_force ? grid_force : kSmallWG)) + 3u) & ~3u;
-        tl = tl < 4u ? 4u : (tl > (uint32_t)kTile ? (uint32_t)kTile : tl);
-        const uint32_t nt = (n + tl - 1) / tl;
-        tiles_per_wg = grid_force ? (nt + grid_force - 1) / grid_force : (uint32_t)kWaves6;
-        grid = (nt + tiles_per_wg - 1) / tiles_per_wg;
-    } else {
-        echo6_geometry(n, grid_force ? grid_force : ncu, &grid, &tiles_per_wg);
-    }
+    if (small) echo6_small_tiling(n, tile, grid_force, &tl, &tiles_per_wg, &grid);
+    else echo6_geometry(n, wgs, &grid, &tiles_per_wg);
     const hipStream_t s = (hipStream_t)stream;
-    EchoArgs args;
-    args.umem = (uint8_t*)d_umem;
-    args.umem_size = umem_size;
-    args.descs = d_descs;
-    args.n = n;
-    args.verdicts = d_verdicts;
-    args.recs = d_recs;
-    args.partials = nullptr;
-    args.opts = opts;
     args.tile_live = tl;
     bool fold = false;
     if (d_stats) {
@@ -202,17 +170,10 @@ static int echo_launch(void* d_umem, uint64_t umem_size, const struct xsk_gpu_de
             fold = true;
         }
     }
-    // A batch of more than kMaxRounds rounds per workgroup runs as consecutive launches of about kPieceRounds rounds
-    // each, over consecutive slices of its descriptors: every launch's last round scatters its windows while no
-    // workgroup of that launch still reads, where a long share writes every round's windows into other
-    // workgroups' reads (tools/split_bench.py, profiles/r04/split/: 8 M x 1500 B at 4 KiB, one launch 300.5 us per
-    // M frames, launches of 1 M 264.3; c5's 64 M at 2 KiB 19.50 -> 18.66 ms).
-    constexpr uint32_t kRound = (uint32_t)kWaves6 * kRefTPW, kMaxRounds = 4, kPieceRounds = 2;
+    // a long share runs as consecutive launches over consecutive slices of the descriptors (echo6_pieces)
     const uint32_t ntiles = (n + tl - 1) / tl;
-    uint32_t pieces = 1;
-    if (!small && !args.stats_plain && (tiles_per_wg + kRound - 1) / kRound > kMaxRounds)  // (plain: one writer)
-        pieces = ((tiles_per_wg + kRound - 1) / kRound + kPieceRounds - 1) / kPieceRounds;
-    const uint32_t piece_tiles = (ntiles + pieces - 1) / pieces;
+    uint32_t pieces = 1, piece_tiles = ntiles;
+    if (!small && !args.stats_plain) pieces = echo6_pieces(n, wgs, &piece_tiles);  // (plain: one writer)
     const int slot = timer_begin(device, s);
     for (uint32_t t0 = 0; t0 < ntiles; t0 += piece_tiles) {
         EchoArgs pa = args;
@@ -222,7 +183,7 @@ static int echo_launch(void* d_umem, uint64_t umem_size, const struct xsk_gpu_de
         pa.verdicts = d_verdicts ? d_verdicts + i0 : nullptr;
         pa.recs = d_recs ? d_recs + i0 : nullptr;
         uint32_t pg = grid, ptw = tiles_per_wg;
-        if (pieces > 1) echo6_geometry(pa.n, grid_force ? grid_force : ncu, &pg, &ptw);
+        if (pieces > 1) echo6_geometry(pa.n, wgs, &pg, &ptw);
         if (opts & XSK_GPU_OPT_IPV6)  // dual stack: wire mode that also answers ICMPv6 echo requests (xsk_echo_ds.hip)
             xsk_gpu__echo_ds_launch(&pa, pg, ptw, small, s);
         else if (opts == 0 && !small)

@@ -12,21 +12,19 @@
 #pragma once
 
 #include "../../include/xsk_gpu.h"
+#include "xsk_echo_geometry.h"  // kTile, kWaves6, kRefTPW and the launch geometry
 #include "xsk_echo_kernels.h"
 
 namespace xskgpu {
 namespace {
 
-constexpr int kTile = XSK_GPU_TILE_FRAMES;  // frames per wave tile (= RX_BATCH_SIZE, xsk_utils.h:8)
 constexpr int kWin = 64;                    // header window [a16, a16 + 64), reference and wire mode
 constexpr uint32_t kMaxLen = 1u << 30;      // build-added descriptor sanity bound (XSK_GPU_MAX_LEN)
-constexpr int kWaves6 = 16;                 // waves per workgroup (one workgroup per CU)
 constexpr int kThreads6 = kWaves6 * 64;     // 1024
 constexpr uint32_t kUniMaxNit = 256;        // longest tile of stream_tile_uniform, in row-loads (its 32-bit sums)
 constexpr int kU = 4;                       // 256-B row-loads in flight per lane in the row streams
 constexpr int kUR = 6;                      // the same for the launched kernel's ranked (ragged-tile) streams:
                                             // c4 185.4 -> 182.6 us, c3 / p98 unchanged (profiles/r03/ab_ranked_u6_u8_*)
-constexpr int kRefTPW = 2;                  // reference mode: tiles per wave per round (2048 frames per CU)
 constexpr int kRefHeavy = 512;              // SYNC 2's heavy-frame threshold (bytes)
 constexpr int kRefSlack = 2;                // reference mode: a heavy wave writes once all but 2 waves have read the
                                             // round (SLACK): c4 181.4 -> 176.5 us, c3 274.0 -> 272.9 in-process A/B
@@ -1036,7 +1034,7 @@ __device__ __forceinline__ FrameIn frame_in(const EchoArgs& a, u32x4 dsc, bool i
 // round pays two memory round trips instead of four, with twice the bytes in flight.  The windows go to the
 // two LDS slots, the ICMP sums to the two sum rows, then the header phase of each tile.  Returns false
 // (nothing written) when either tile has a longer frame.
-template <int HEAVY, bool WIRE, bool HB = false, bool V6 = false>
+template <bool WIRE, bool HB = false, bool V6 = false>
 __device__ __forceinline__ bool read_round_short2(const EchoArgs& a, uint32_t t0, uint32_t t1, uint8_t* rows0,
                                                   uint8_t* rows1, uint32_t* sums0, uint32_t* sums1, uint32_t lane,
                                                   Counters& cnt, u32x4* rec, uint32_t* verd, uint32_t* alo,
@@ -1108,8 +1106,8 @@ __device__ __forceinline__ bool read_round_short2(const EchoArgs& a, uint32_t t0
     ahi[0] = d0.y;
     alo[1] = d1.x;
     ahi[1] = d1.y;
-    round_long += (uint32_t)__popcll(__ballot(in0 && F0.len >= (uint32_t)HEAVY)) +
-                  (uint32_t)__popcll(__ballot(in1 && F1.len >= (uint32_t)HEAVY));
+    round_long += (uint32_t)__popcll(__ballot(in0 && F0.len >= (uint32_t)kRefHeavy)) +
+                  (uint32_t)__popcll(__ballot(in1 && F1.len >= (uint32_t)kRefHeavy));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();  // the sums / windows are rewritten by the next round
     return true;
@@ -1126,34 +1124,49 @@ __device__ __forceinline__ bool read_round_short2(const EchoArgs& a, uint32_t t0
 //
 // echo6_body: the work over the tiles [t_begin, t_end) of one workgroup (every wave of the workgroup calls
 // it with the same range); echo_round_kernel runs it once per workgroup on its static share, the
-// low-latency resident kernel (xsk_lowlat.hip) once per doorbell.
-//   TPW   tiles per wave per round (2; sub-tiles 1)
-//   SYNC  how a wave enters its write phase.  0: at once (one-round small batches); 2: a wave at least half
-//         of whose frames this round have >= HEAVY bytes waits until every wave of the workgroup but SLACK has
-//         read the round (LDS arrival counter), lighter waves go ahead -- the phase separation pays where reads
-//         dominate, and costs latency hiding where frames are short
-//   WIRE  the wire-format mode (a.opts != 0): the reference mode's streams and rounds with wire_header_phase64
-//   SUBT  tiles of a.tile_live frames (small batches: the batch spreads over every wave)
-//   TRACE wave 0 stamps the body's phase boundaries into a.trace (the low-latency kernel's diagnostics)
-//   DLDS  the descriptors may already be in the LDS (a.desc_in_lds, the low-latency kernel's first poll)
-//   WT    write-phase windows and records stored write-through (sc1 raw buffer stores)
-//   V6    the dual-stack kernels (XSK_GPU_OPT_IPV6): wire mode whose header phase also answers ICMPv6 echo requests
+// low-latency resident kernel (xsk_lowlat.hip) once per doorbell.  Its switches are the static members of a config
+// type C, which every kernel names from one of two families (RoundCfg below, ResidentCfg in xsk_lowlat.hip):
+//   TPW    tiles per wave per round (2; sub-tiles 1)
+//   SYNC   how a wave enters its write phase.  0: at once (one-round small batches); 2: a wave at least half
+//          of whose frames this round have >= kRefHeavy bytes waits until every wave of the workgroup but SLACK has
+//          read the round (LDS arrival counter), lighter waves go ahead -- the phase separation pays where reads
+//          dominate, and costs latency hiding where frames are short
+//   WIRE   the wire-format mode (a.opts != 0): the reference mode's streams and rounds with wire_header_phase64
+//   SUBT   tiles of a.tile_live frames (small batches: the batch spreads over every wave)
+//   TRACE  wave 0 stamps the body's phase boundaries into a.trace (the low-latency kernel's diagnostics)
+//   DLDS   the descriptors may already be in the LDS (a.desc_in_lds, the low-latency kernel's first poll)
+//   WT     write-phase windows and records stored write-through (sc1 raw buffer stores)
+//   UR     row-loads in flight per lane in the ranked streams (kUR; kU where rounds are short)
+//   USPLIT the uniform stream's row-loads of a step in equal batches (stream_tile_uniform's SPLIT)
+//   PRIO   a stream batch's address work and loads at s_setprio 2
+//   SLACK  SYNC 2: waves of the workgroup a heavy wave does not wait for
+//   HB     the header phase reads and patches an aligned wave's windows with b128 LDS accesses (header_phase_ref)
+//   V6     the dual-stack kernels (XSK_GPU_OPT_IPV6): wire mode whose header phase also answers ICMPv6 echo requests
 // The per-tile stream choices: tiles whose frames all fit their 64-B windows (c2)
 // skip the row stream (and two such tiles of a round are read together, PAIR), ping-size tiles (every frame
 // within 128 B) are read by 8-lane groups, uniform long tiles (c3, c5) take masks computed once per tile,
 // ragged tiles (c4) the ranked step-packed streams.
 // ================================================================================================
-template <int TPW, int SYNC, bool WIRE, bool SUBT, bool TRACE, bool DLDS, bool WT, int HEAVY, int UR = kU,
-          bool USPLIT = false, bool PRIO = false, int SLACK = 0, bool HB = false, bool V6 = false>
-__device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, uint32_t t_end, Echo6Smem<TPW>& sm) {
-    static_assert(SYNC == 0 || SYNC == 2, "write phases: at once (0) or heavy waves wait for the round (2)");
-    static_assert(SLACK >= 0 && SLACK < kWaves6, "SLACK: waves a heavy wave does not wait for");
+// The launched kernels' family: rounds of two 64-frame tiles per wave (SUBT false), or sub-tiles that a wave writes at
+// once (SUBT true).  The arguments behind V6 are echo_round_kernel's, for the tuning library's A/B variants.
+template <bool WIRE_, bool SUBT_, bool V6_ = false, int UR_ = SUBT_ ? kU : kUR, bool USPLIT_ = !SUBT_,
+          bool PRIO_ = !SUBT_, int SLACK_ = SUBT_ ? 0 : kRefSlack, bool HB_ = true>
+struct RoundCfg {
+    static constexpr int TPW = SUBT_ ? 1 : kRefTPW, SYNC = SUBT_ ? 0 : 2, UR = UR_, SLACK = SLACK_;
+    static constexpr bool WIRE = WIRE_, SUBT = SUBT_, TRACE = false, DLDS = false, WT = !SUBT_, USPLIT = USPLIT_,
+                          PRIO = PRIO_, HB = HB_, V6 = V6_;
+};
+
+template <class C>
+__device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, uint32_t t_end, Echo6Smem<C::TPW>& sm) {
+    static_assert(C::SYNC == 0 || C::SYNC == 2, "write phases: at once (0) or heavy waves wait for the round (2)");
+    static_assert(C::SLACK >= 0 && C::SLACK < kWaves6, "SLACK: waves a heavy wave does not wait for");
     constexpr int U = kU;
-    constexpr bool PAIR = TPW == 2 && !SUBT;  // paired short tiles (header_phase_ref / wire_header_phase64)
+    constexpr bool PAIR = C::TPW == 2 && !C::SUBT;  // paired short tiles (header_phase_ref / wire_header_phase64)
     constexpr uint32_t kRowW = (uint32_t)kWin;  // LDS row (header window) bytes
     auto& s_hdr = sm.hdr;
     uint32_t& s_arrive = sm.arrive;
-    if (SYNC == 2) {
+    if (C::SYNC == 2) {
         if (threadIdx.x == 0) s_arrive = 0u;
         __syncthreads();
     }
@@ -1162,23 +1175,24 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
     const uint32_t wave = uniform(threadIdx.x >> 6);
     FrameMeta6* meta = sm.meta[wave];
     uint32_t* sums_ic = sm.sum[wave][0];
-    constexpr uint32_t kRound = (uint32_t)kWaves6 * TPW;
+    constexpr uint32_t kRound = (uint32_t)kWaves6 * C::TPW;
     Counters cnt;
     uint32_t lane = threadIdx.x & 63u;
     for (uint32_t r0 = t_begin; r0 < t_end; r0 += kRound) {  // rounds, workgroup-uniform
         // slot i of this round: wave w streams tile r0 + i * 16 + w when it is below t_end
-        u32x4 rec[TPW];
-        uint32_t verd[TPW], alo[TPW], ahi[TPW];
-        uint64_t wbm[TPW];
-        uint32_t round_long = 0;  // SYNC 2: frames of >= HEAVY bytes this wave read this round (uniform)
+        u32x4 rec[C::TPW];
+        uint32_t verd[C::TPW], alo[C::TPW], ahi[C::TPW];
+        uint64_t wbm[C::TPW];
+        uint32_t round_long = 0;  // SYNC 2: frames of >= kRefHeavy bytes this wave read this round (uniform)
         // ================= read phase =================
         bool paired = false;
         if (PAIR && r0 + wave < t_end && r0 + (uint32_t)kWaves6 + wave < t_end)  // wave-uniform
-            paired = read_round_short2<HEAVY, WIRE, HB, V6>(a, r0 + wave, r0 + (uint32_t)kWaves6 + wave, s_hdr[wave][0],
-                                              s_hdr[wave][TPW > 1 ? 1 : 0], sm.sum[wave][0], sm.sum[wave][1], lane,
-                                              cnt, rec, verd, alo, ahi, wbm, round_long);
+            paired = read_round_short2<C::WIRE, C::HB, C::V6>(a, r0 + wave, r0 + (uint32_t)kWaves6 + wave, s_hdr[wave][0],
+                                                              s_hdr[wave][C::TPW > 1 ? 1 : 0], sm.sum[wave][0],
+                                                              sm.sum[wave][1], lane, cnt, rec, verd, alo, ahi, wbm,
+                                                              round_long);
 #pragma unroll
-        for (int i = 0; i < TPW; ++i) {
+        for (int i = 0; i < C::TPW; ++i) {
             if (PAIR && paired) continue;  // wave-uniform: both tiles are done
             u32x4 rec_o;
             uint32_t verd_o, alo_o, ahi_o;
@@ -1194,11 +1208,11 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
                 asm volatile("" : "+v"(lane));
                 uint8_t* rows = s_hdr[wave][i];
                 const uint32_t q = lane >> 4, k = lane & 15u;
-                const uint32_t fi = t * (SUBT ? a.tile_live : (uint32_t)kTile) + lane;
-                const bool in_n = (!SUBT || lane < a.tile_live) && fi < a.n;  // a live frame of the batch
+                const uint32_t fi = t * (C::SUBT ? a.tile_live : (uint32_t)kTile) + lane;
+                const bool in_n = (!C::SUBT || lane < a.tile_live) && fi < a.n;  // a live frame of the batch
                 // ---- 1. descriptors (xsk_receive.c:222-223): lane i <- frame t*64+i ----------------------
                 u32x4 dsc = u32x4{0u, 0u, 0u, 0u};
-                if (DLDS && a.desc_in_lds) {
+                if (C::DLDS && a.desc_in_lds) {
                     if (in_n) dsc = sm.desc[fi];  // n <= 64: fi < 64
                 } else if (in_n) {
                     dsc = *(const u32x4*)(a.descs + fi);
@@ -1207,9 +1221,9 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
                 const uint32_t len = dsc.z;
                 // reference mode reads bytes [0, 38) whenever len >= 20 (xsk_receive.c:120-157); wire mode
                 // reads only [addr, addr + len) plus the window
-                const uint64_t need = WIRE ? len : (len >= 20 ? (len > 38 ? len : 38) : len);
+                const uint64_t need = C::WIRE ? len : (len >= 20 ? (len > 38 ? len : 38) : len);
                 const bool ok = in_n && len <= kMaxLen && addr <= a.umem_size && need <= a.umem_size - addr;
-                const bool parse = ok && len >= (WIRE ? 14u : 20u);
+                const bool parse = ok && len >= (C::WIRE ? 14u : 20u);
                 const uint64_t a16 = addr & ~15ull;
                 const uint32_t off = (uint32_t)addr & 15u;
                 const uint32_t rowhi = parse ? off + len : 0u;
@@ -1240,8 +1254,8 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
                 }
                 alo_o = dsc.x;
                 ahi_o = dsc.y;
-                if (SYNC == 2) round_long += (uint32_t)__popcll(__ballot(in_n && len >= (uint32_t)HEAVY));
-                if (TRACE && threadIdx.x == 0 && i == 0) a.trace[0] = wall_clock64();  // descriptors parsed
+                if (C::SYNC == 2) round_long += (uint32_t)__popcll(__ballot(in_n && len >= (uint32_t)kRefHeavy));
+                if (C::TRACE && threadIdx.x == 0 && i == 0) a.trace[0] = wall_clock64();  // descriptors parsed
                 // ---- 2. stream every row byte once; windows -> LDS rows, row sums -> LDS -----------------
                 if (__ballot(nit != 0u) != 0ull) {
                     __builtin_amdgcn_wave_barrier();
@@ -1302,12 +1316,12 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
                     } else if (__ballot(nit != 0u && nit != uniform(max_nit_lane(nit))) != 0ull ||
                                uniform(max_nit_lane(nit)) < (uint32_t)U) {
                         // ragged tile (or one too short to fill a batch of U row-loads): ranked streams
-                        if (fast) stream_tile_sorted<UR, true, true, PRIO>(a, ld.r, meta, sm.sort[wave], rows, sums_ic, nit, lane);
-                        else stream_tile_sorted<UR, false, true, PRIO>(a, ld.r, meta, sm.sort[wave], rows, sums_ic, nit, lane);
+                        if (fast) stream_tile_sorted<C::UR, true, true, C::PRIO>(a, ld.r, meta, sm.sort[wave], rows, sums_ic, nit, lane);
+                        else stream_tile_sorted<C::UR, false, true, C::PRIO>(a, ld.r, meta, sm.sort[wave], rows, sums_ic, nit, lane);
                     } else if (fast && uniform(max_nit_lane(nit)) <= kUniMaxNit && __ballot(!parse) == 0ull &&
                                __ballot(ukey != uniform(ukey)) == 0ull) {
                         // (longer uniform tiles take the per-step streams below, whose sums are 64-bit)
-                        stream_tile_uniform<U, USPLIT, PRIO>(ld.r, meta, rows, sums_ic, uniform(nit), uniform(off) + 34u,
+                        stream_tile_uniform<U, C::USPLIT, C::PRIO>(ld.r, meta, rows, sums_ic, uniform(nit), uniform(off) + 34u,
                                                              uniform(rowhi), lane);
                     } else {
                         // every frame the same number of row-loads, but different offsets or ends: per-step streams
@@ -1338,15 +1352,15 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
 
                 // ---- 3. header phase (lane = frame); the window stays patched in LDS ---------------------
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (TRACE && threadIdx.x == 0 && i == 0) a.trace[1] = wall_clock64();  // frames streamed
+                if (C::TRACE && threadIdx.x == 0 && i == 0) a.trace[1] = wall_clock64();  // frames streamed
                 __builtin_amdgcn_wave_barrier();
                 const uint32_t ic_raw = nit ? sums_ic[lane] : 0u;
                 bool wb;
-                if (WIRE)
-                    wb = wire_header_phase64<HB, V6>(a, rows + lane * kRowW, ic_raw, addr, len, ok, in_n, wend, cnt, &rec_o,
+                if (C::WIRE)
+                    wb = wire_header_phase64<C::HB, C::V6>(a, rows + lane * kRowW, ic_raw, addr, len, ok, in_n, wend, cnt, &rec_o,
                                              &verd_o);
                 else
-                    wb = header_phase_ref<HB>(a, rows + lane * kWin, ic_raw, addr, len, in_n, ok, parse, cnt, &rec_o,
+                    wb = header_phase_ref<C::HB>(a, rows + lane * kWin, ic_raw, addr, len, in_n, ok, parse, cnt, &rec_o,
                                           &verd_o);
                 wbm_o = __ballot(wb);
             } while (0);
@@ -1359,27 +1373,27 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
             wbm[i] = wbm_o;
         }
 
-        if (TRACE && threadIdx.x == 0) a.trace[2] = wall_clock64();  // header phase done
+        if (C::TRACE && threadIdx.x == 0) a.trace[2] = wall_clock64();  // header phase done
         // ================= write phase =================
-        if (SYNC == 2) {
+        if (C::SYNC == 2) {
             ++rounds_done;
             if (lane == 0) atomicAdd(&s_arrive, 1u);
-            if (uniform(round_long) * 2u >= (uint32_t)(kTile * TPW)) {  // at least half its frames long
+            if (uniform(round_long) * 2u >= (uint32_t)(kTile * C::TPW)) {  // at least half its frames long
                 // (every wave but SLACK: the last waves of a round are usually ragged ones still streaming)
                 while (__hip_atomic_load(&s_arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) <
-                       rounds_done * (uint32_t)kWaves6 - (uint32_t)SLACK)
+                       rounds_done * (uint32_t)kWaves6 - (uint32_t)C::SLACK)
                     __builtin_amdgcn_s_sleep(2);
             }
         }
 #pragma unroll
-        for (int i = 0; i < TPW; ++i) {
+        for (int i = 0; i < C::TPW; ++i) {
             const uint32_t t = r0 + (uint32_t)i * kWaves6 + wave;
             if (t >= t_end) continue;
             const uint8_t* rows = s_hdr[wave][i];
             if (wbm[i]) {  // patched windows: 16 frames x 64 B per wave-store, whole 64-B sectors
                 // WT: the 4 GiB region of the tile's first written window; every written window inside it?
-                const uint32_t hi_u = WT ? rdlane(ahi[i], (uint32_t)__builtin_ctzll(wbm[i])) : 0u;
-                const bool wt_tile = WT && __ballot(((wbm[i] >> lane) & 1ull) &&
+                const uint32_t hi_u = C::WT ? rdlane(ahi[i], (uint32_t)__builtin_ctzll(wbm[i])) : 0u;
+                const bool wt_tile = C::WT && __ballot(((wbm[i] >> lane) & 1ull) &&
                                                     (ahi[i] != hi_u || alo[i] > 0xFFFFFFC0u)) == 0ull;
                 const __amdgpu_buffer_rsrc_t wrs =
                     __builtin_amdgcn_make_buffer_rsrc((void*)(a.umem + ((uint64_t)hi_u << 32)), (short)0, -1, kRsrcFlags);
@@ -1392,18 +1406,18 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
                     if ((wbm[i] >> f) & 1ull) {
                         const uint64_t fa = (uint64_t)flo | ((uint64_t)fhi << 32);
                         const u32x4 w = *(const u32x4*)(rows + f * kRowW + 16u * kk);
-                        if (WT && wt_tile) __builtin_amdgcn_raw_buffer_store_b128(w, wrs, (int)(flo + 16u * kk), 0, kAuxSC1);
+                        if (C::WT && wt_tile) __builtin_amdgcn_raw_buffer_store_b128(w, wrs, (int)(flo + 16u * kk), 0, kAuxSC1);
                         else *(u32x4*)(a.umem + fa + 16u * kk) = w;
                     }
                 }
             }
-            const uint32_t fi = t * (SUBT ? a.tile_live : (uint32_t)kTile) + lane;
-            if ((!SUBT || lane < a.tile_live) && fi < a.n) {
+            const uint32_t fi = t * (C::SUBT ? a.tile_live : (uint32_t)kTile) + lane;
+            if ((!C::SUBT || lane < a.tile_live) && fi < a.n) {
                 if (a.recs) {
-                    if (WT)
+                    if (C::WT)
                         __builtin_amdgcn_raw_buffer_store_b128(
                             rec[i],
-                            __builtin_amdgcn_make_buffer_rsrc((void*)((u32x4*)a.recs + (uint64_t)uniform(t) * (SUBT ? a.tile_live : (uint32_t)kTile)),
+                            __builtin_amdgcn_make_buffer_rsrc((void*)((u32x4*)a.recs + (uint64_t)uniform(t) * (C::SUBT ? a.tile_live : (uint32_t)kTile)),
                                                               (short)0, -1, kRsrcFlags),
                             (int)(lane * 16u), 0, kAuxSC1);
                     else ((u32x4*)a.recs)[fi] = rec[i];
@@ -1414,39 +1428,39 @@ __device__ __forceinline__ void echo6_body(const EchoArgs& a, uint32_t t_begin, 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();  // LDS rows are rewritten by the next round
     }
-    if (TRACE && threadIdx.x == 0) a.trace[3] = wall_clock64();  // write phase issued
+    if (C::TRACE && threadIdx.x == 0) a.trace[3] = wall_clock64();  // write phase issued
     store_counters(a, cnt, sm.cnt, wave, lane);
-    if (TRACE && threadIdx.x == 0) a.trace[4] = wall_clock64();  // counters added
+    if (C::TRACE && threadIdx.x == 0) a.trace[4] = wall_clock64();  // counters added
 }
 
 // The launched transform: one 16-wave workgroup per CU, each the same contiguous share of tiles_per_wg
-// tiles (echo6_geometry); reference or wire mode (WIRE), large batches or one workgroup of sub-tiles of
+// tiles (echo6_geometry, xsk_echo_geometry.h); reference or wire mode (WIRE), large batches or one workgroup of sub-tiles of
 // a.tile_live frames (SUBT: writes as soon as a wave has read, plain stores).  Wire batches run on the same 64-B
 // windows (44 / 280 / 185 us for c2 / c3 / c4 against 71 / 298 / 215 on the 128-B windows of rounds 1-4, in-process
 // A/B, profiles/r04/wire64/).
 template <bool WIRE, bool SUBT, int UR = SUBT ? kU : kUR, bool USPLIT = !SUBT, bool PRIO = !SUBT,
           int SLACK = SUBT ? 0 : kRefSlack, bool HB = true>
 __global__ __launch_bounds__(kThreads6, 1) void echo_round_kernel(EchoArgs a, uint32_t tiles_per_wg) {
-    constexpr int TPW = SUBT ? 1 : kRefTPW;
-    __shared__ Echo6Smem<TPW> sm;
+    using Cfg = RoundCfg<WIRE, SUBT, false, UR, USPLIT, PRIO, SLACK, HB>;
+    __shared__ Echo6Smem<Cfg::TPW> sm;
     const uint32_t tl = SUBT ? a.tile_live : (uint32_t)kTile;
     const uint32_t ntiles = (a.n + tl - 1) / tl;
     const uint32_t t_begin = blockIdx.x * tiles_per_wg;
     const uint32_t t_end = min(ntiles, t_begin + tiles_per_wg);
-    echo6_body<TPW, SUBT ? 0 : 2, WIRE, SUBT, false, false, !SUBT, kRefHeavy, UR, USPLIT, PRIO, SLACK, HB>(a, t_begin,
-                                                                                                        t_end, sm);
+    echo6_body<Cfg>(a, t_begin, t_end, sm);
 }
 
-// Round kernel geometry: one workgroup per CU (fewer for small batches), equal contiguous tile shares.
-constexpr uint32_t kMaxCuBound = 1024;  // workspace bound for the round kernel's one-workgroup-per-CU grid
-inline void echo6_geometry(uint32_t n, uint32_t num_cu, uint32_t* grid, uint32_t* tiles_per_wg) {
-    const uint32_t ntiles = (n + kTile - 1) / kTile;
-    uint32_t g = num_cu < 1 ? 1 : num_cu;
-    if (g > ntiles) g = ntiles < 1 ? 1 : ntiles;
-    const uint32_t per = (ntiles + g - 1) / g;
-    *tiles_per_wg = per < 1 ? 1 : per;
-    *grid = (ntiles + *tiles_per_wg - 1) / *tiles_per_wg;
-    if (*grid < 1) *grid = 1;
+// The argument rules every transform entry point shares (include/xsk_gpu.h), with no device call, and the EchoArgs of
+// a batch of n descriptors that passes them (no counters; the members behind opts at their defaults).  false: -EINVAL.
+inline bool echo_args_init(EchoArgs* a, void* d_umem, uint64_t umem_size, const xsk_gpu_desc* d_descs, uint32_t n,
+                           uint32_t opts, uint8_t* d_verdicts, xsk_gpu_rec* d_recs) {
+    if ((opts & ~XSK_GPU_OPT_MASK) || n > XSK_GPU_MAX_BATCH) return false;  // (0x8 is reserved)
+    if (!d_umem || !d_descs || ((uintptr_t)d_umem & 15u) || (umem_size & 15u) || ((uintptr_t)d_descs & 15u) ||
+        ((uintptr_t)d_recs & 15u))
+        return false;
+    if (umem_size >> 48) return false;  // FrameMeta6 carries 48-bit UMEM offsets (both modes)
+    *a = EchoArgs{(uint8_t*)d_umem, umem_size, d_descs, n, d_verdicts, d_recs, /*partials*/ nullptr, opts};
+    return true;
 }
 
 }  // namespace

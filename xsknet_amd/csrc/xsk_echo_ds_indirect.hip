@@ -1,6 +1,6 @@
 // xsk_echo_ds_indirect.hip — the dual-stack instance (XSK_GPU_OPT_IPV6) of xsk_gpu_echo_dev_indirect()'s kernels:
-// echo_ds_kernel<false> of xsk_echo_ds.hip behind the prologue of xsk_echo_indirect.hip (the count read from device
-// memory, the workgroup's share of it: xsk_echo_indirect.h).  A file of its own for the reason xsk_echo_ds.hip is one:
+// echo_ds_kernel<false>'s config, RoundCfg<true, false, true>, behind the prologue of xsk_echo_indirect.hip (the count
+// read from device memory, the workgroup's share of it: xsk_echo_indirect.h).  A file of its own as xsk_echo_ds.hip is:
 // the round body with the IPv6 phase needs the larger `#pragma unroll` budget (Makefile), which must not reach the
 // other kernels.
 #include "xsk_echo_device.h"
@@ -18,8 +18,7 @@ __global__ __launch_bounds__(kThreads6, 1) void echo_ds_indirect_kernel(EchoArgs
     uint32_t t_begin, t_end;
     ind_share(a.n, gridDim.x, blockIdx.x, &t_begin, &t_end);
     if (t_begin >= t_end) return;  // workgroup-uniform
-    echo6_body<kRefTPW, 2, true, false, false, false, true, kRefHeavy, kUR, true, true, kRefSlack, true, true>(
-        a, t_begin, t_end, sm);
+    echo6_body<RoundCfg<true, false, true>>(a, t_begin, t_end, sm);
 }
 
 }  // namespace

@@ -56,6 +56,14 @@ constexpr bool kYield = XSK_LL_YIELD != 0;
 constexpr int kLLTPW = 1;                    // 16 tiles = 1024 frames per doorbell, one round
 constexpr int kLLSync = 0;                   // one round: write as soon as the wave has read
 
+// echo6_body's config for the resident kernels: one round of sub-tiles, phase stamps, doorbell descriptors, plain stores
+template <bool WIRE_, bool V6_ = false>
+struct ResidentCfg {
+    static constexpr int TPW = kLLTPW, SYNC = kLLSync, UR = kU, SLACK = 0;
+    static constexpr bool WIRE = WIRE_, SUBT = true, TRACE = true, DLDS = true, WT = false, USPLIT = false,
+                          PRIO = false, HB = true, V6 = V6_;
+};
+
 constexpr int kPollCopies = 2;  // doorbell words (and first-64 descriptor blocks) polled in turn
 
 // workgroups of resident grids running now, in this process (device memory; each workgroup adds one when it starts
@@ -285,8 +293,7 @@ __global__ __launch_bounds__(kThreads6, 1) void lowlat_kernel(LowlatArgs L) {
         if (ntiles)
             // wire mode on the reference form's 64-B windows and streams with wire_header_phase64 (the 128-B form took
             // 11.6 us per 64 x 64-B call with every option against 8.7 in reference mode, profiles/r04/wll/)
-            echo6_body<kLLTPW, kLLSync, WIRE, true, true, true, false, kRefHeavy, kU, false, false, 0, true>(a, 0u,
-                                                                                                          ntiles, sm);
+            echo6_body<ResidentCfg<WIRE>>(a, 0u, ntiles, sm);
         // the two polls' registers live across the body: a batch is taken while the other poll is still in
         // flight, and registers the compiler reused would first have to wait for it to land
         asm volatile("" ::"v"(P.cA), "v"(P.aA), "v"(P.bA), "v"(P.cB), "v"(P.aB), "v"(P.bB), "v"(P.yA), "v"(P.yB));
@@ -382,8 +389,7 @@ __global__ __launch_bounds__(kThreads6, 1) void resident_ds_kernel(LowlatArgs L)
         if (ntiles)
             // wire mode on the reference form's 64-B windows and streams with wire_header_phase64 (the 128-B form took
             // 11.6 us per 64 x 64-B call with every option against 8.7 in reference mode, profiles/r04/wll/)
-            echo6_body<kLLTPW, kLLSync, true, true, true, true, false, kRefHeavy, kU, false, false, 0, true, /*V6*/ true>(
-                a, 0u, ntiles, sm);
+            echo6_body<ResidentCfg<true, /*V6*/ true>>(a, 0u, ntiles, sm);
         // the two polls' registers live across the body: a batch is taken while the other poll is still in
         // flight, and registers the compiler reused would first have to wait for it to land
         asm volatile("" ::"v"(P.cA), "v"(P.aA), "v"(P.bA), "v"(P.cB), "v"(P.aB), "v"(P.bB), "v"(P.yA), "v"(P.yB));
