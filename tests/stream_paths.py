@@ -6,6 +6,13 @@ nit, ukey, span -- and walks the same if / else chain, so a GPU test can assert 
 the path it is about before the GPU is asked.  The frame builders are thin wrappers over make_wire_golden.build and
 make_v6_golden.build6: valid echo requests of a given total length with a 0xFF, 0x00 or seeded random payload, placed
 at addr = i * stride + off_i in a UMEM of seeded random bytes, so that a stray write shows.
+
+resident_tiling() / resident_tile_paths() restate the tiling of the resident (LOWLAT) kernels -- serving workgroups,
+slices and frames per tile as xsk_gpu__lowlat_post posts them and the kernels of xsk_lowlat.hip derive them -- so the
+same assertion holds for a doorbell batch.  The users: tests/test_gpu_stream_paths.py and tests/test_gpu_long_frames.py
+(the launched round and sub-tile kernels), tests/test_gpu_resident_paths.py (lowlat_kernel<false>, lowlat_kernel<true>,
+resident_ds_kernel) and tests/test_gpu_indirect_paths.py (echo_indirect_kernel<false>, <true>, echo_ds_indirect_kernel);
+tests/test_stream_paths.py pins the selector, the restated tiling and the tables on the CPU.
 """
 import functools
 
@@ -86,6 +93,66 @@ def sub_tile_live(n: int, grid: int) -> int:
     wg = grid if grid else 16
     tl = ((n + 16 * wg - 1) // (16 * wg) + 3) & ~3
     return min(max(tl, 4), TILE)
+
+
+# ---- the resident (LOWLAT) kernels' tiling --------------------------------------------------------------------------
+LL_WG = 4            # XSK_GPU__LL_WG: workgroups of the resident grid
+LOWLAT_MAX = 1024    # XSK_GPU_LOWLAT_MAX: the largest doorbell batch
+LL_WAVES = 16        # kWaves6: waves of one resident workgroup
+
+
+def _capped_bytes(descs) -> int:
+    return int(np.minimum(np.asarray(descs["len"], np.uint64), 4096).sum())
+
+
+def ll_groups(descs) -> int:
+    """xsk_gpu__ll_groups (xsk_lowlat_proto.h): the leader alone up to 64 frames, and up to 128 frames of at most
+    16 KiB (each frame counted up to 4096 B); every workgroup above."""
+    n = len(descs)
+    if n <= 64 or (n <= 128 and _capped_bytes(descs) <= 16 << 10):
+        return 1
+    return LL_WG
+
+
+def ll_slice(n: int, w: int, g: int):
+    """xsk_gpu__ll_slice: workgroup g's frames [f0, f1) of an n-frame batch over w workgroups."""
+    per = ((n + w - 1) // w + 3) & ~3
+    a = min(g * per, n)
+    return a, min(a + per, n)
+
+
+def small_tile(descs, max_waves: int = LL_WAVES) -> int:
+    """xsk_gpu__small_tile_w (xsk_gpu_internal.h): frames per wave, 8 KiB of frame bytes (a frame counted up to
+    4096 B) per wave, 1 .. max_waves waves, rounded up to a multiple of 4 and clamped to 4 .. 64."""
+    n = len(descs)
+    waves = min(max((_capped_bytes(descs) + 8191) // 8192, 1), max_waves)
+    t = ((n + waves - 1) // waves + 3) & ~3
+    return min(max(t, 4), TILE)
+
+
+def resident_tiling(descs, groups: int = 0, tile_frames: int = 0):
+    """(frames per tile, [(f0, f1) per serving workgroup]) of a doorbell batch, as xsk_gpu__lowlat_post (xsk_lowlat.hip)
+    posts it and lowlat_kernel / resident_ds_kernel derive it: w = xsk_gpu__ll_groups, or min(groups, n) when tuned;
+    one tile size for every slice, xsk_gpu__small_tile of slice 0's descriptors, or tile_frames when tuned
+    (xsk_gpu__lowlat_tune); workgroup g serves slice g in tiles that start at the slice's first frame (a slice past
+    the batch's end is empty: f0 == f1)."""
+    n = len(descs)
+    assert 0 < n <= LOWLAT_MAX and 0 <= groups <= LL_WG
+    assert tile_frames == 0 or (4 <= tile_frames <= TILE and tile_frames % 4 == 0)
+    w = min(groups, n) if groups else ll_groups(descs)
+    slices = [ll_slice(n, w, g) for g in range(w)]
+    f0, f1 = slices[0]
+    tl = tile_frames if tile_frames else 4 * (small_tile(descs[f0:f1]) // 4)
+    return tl, slices
+
+
+def resident_tile_paths(descs, umem_size: int, wire: bool, groups: int = 0, tile_frames: int = 0):
+    """tile_paths() of a doorbell batch in the resident kernels' tiling: one path per tile, slice after slice."""
+    tl, slices = resident_tiling(descs, groups, tile_frames)
+    out = []
+    for f0, f1 in slices:
+        out += tile_paths(descs[f0:f1], umem_size, wire, tl)
+    return out
 
 
 # ---- frames ---------------------------------------------------------------------------------------------------
@@ -220,6 +287,17 @@ def ragged_tile(kind: str, lo: int = 60_000, hi: int = 300_000):
     return [(lo + (hi - lo) * ((j * 37) % TILE) // (TILE - 1), j % 16, kind) for j in range(TILE)]
 
 
+# The long-frame batches of the indirect-kernel matrix: name -> (tiles, frames, tile_paths in reference and wire mode).
+# "long": past 128 KiB, where only 64-bit sums hold (two equal-frame tiles, a per-step one, a ranked one, 41 fillers);
+# "limit": 64 KiB frames, the longest stream_tile_uniform takes (256 row-loads at offset 0; offset 6 is one too many).
+INDIRECT_LONG_BATCHES = {
+    "long": (lambda: uniform_tiles(131_200, "ff", (0, 6)) + [per_step_tile(131_200, "random")]
+             + [ragged_tile("zero", 60_000, 131_200)], 4 * 64 + 41,
+             ["per_step", "per_step", "per_step", "sorted", "short"]),
+    "limit": (lambda: uniform_tiles(65_536, "ff", (0, 6)), 2 * 64 + 41, ["uniform", "per_step", "short"]),
+}
+
+
 # ordinary lengths: shape name -> (expected path, per-frame (length, offset) of one tile as a function of j, v6)
 def shape_tile(shape: str, v6: bool, off: int = 0):
     """64 (length, offset) pairs of one tile of `shape` and the path it must take."""
@@ -242,6 +320,35 @@ def shape_tile(shape: str, v6: bool, off: int = 0):
 SHAPES = ("mid_uni", "mid", "uniform", "per_step", "sorted", "short")
 SHAPE_OFFS = {"mid_uni": (0, 6, 13), "uniform": (0, 6, 15), "short": (0, 1), "mid": (0,), "per_step": (0,),
               "sorted": (0,)}
+
+
+# The three doorbell batches the resident-kernel matrix (tests/test_gpu_resident_paths.py) cuts from
+# shape_batch(shape, v6, off, 1105): (name, frames, lowlat_tune groups, lowlat_tune tile_frames).  "full" and "poll" run
+# at the product's own geometry (poll: <= 64 frames, the descriptors the leader's poll brought); "tuned" is one
+# workgroup and whole 64-frame tiles, the only geometry in which a resident kernel takes stream_tile_uniform.
+RESIDENT_GEOMETRIES = (("full", 1024, 0, 0), ("poll", 64, 0, 0), ("tuned", 1024, 1, 64))
+
+
+def resident_table(shape: str, v6: bool):
+    """{geometry name: {path: tiles}}: what resident_tile_paths must give for the three RESIDENT_GEOMETRIES batches of
+    shape_batch(shape, v6, off, 1105), at every offset of SHAPE_OFFS[shape], in reference and in wire mode.  Worked out
+    from xsk_gpu__ll_groups / xsk_gpu__ll_slice / xsk_gpu__small_tile: 1024 ping-size frames are 4 slices of 256 frames
+    in 64-frame tiles (4 x 4 tiles), 1024 frames of 1500 B 4 slices in 16-frame tiles (4 x 16: a tile with dead lanes is
+    never `uniform`), 64 frames of 1500 B one slice in 8-frame tiles (12 waves); two of the `sorted` shape's
+    8-frame tiles hold one row-load count each (lengths 19 B apart).  IPv6 `short` frames behind VLAN tags (tile 3)
+    are longer than their window: that tile is `mid`."""
+    if shape in ("mid_uni", "mid"):
+        return {"full": {shape: 16}, "poll": {shape: 1}, "tuned": {shape: 16}}
+    if shape == "short":
+        full = {"short": 15, "mid": 1} if v6 else {"short": 16}
+        return {"full": full, "poll": {"short": 1}, "tuned": full}
+    if shape == "uniform":
+        return {"full": {"per_step": 64}, "poll": {"per_step": 8}, "tuned": {"uniform": 16}}
+    if shape == "per_step":
+        return {"full": {"per_step": 64}, "poll": {"per_step": 8}, "tuned": {"per_step": 16}}
+    if shape == "sorted":
+        return {"full": {"sorted": 64}, "poll": {"sorted": 6, "per_step": 2}, "tuned": {"sorted": 16}}
+    raise ValueError(shape)
 
 
 def shape_batch(shape: str, v6: bool, off: int, n: int, stride: int = 2048, seed: int = 1):

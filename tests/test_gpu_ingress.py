@@ -103,18 +103,47 @@ def test_indirect_transform(opts, n_max, count):
 
 # ---- the piece rule ----------------------------------------------------------------------------------------------
 
-def test_indirect_piece_rule():
+def six_mask(frames: np.ndarray, lens: np.ndarray, opts: int) -> np.ndarray:
+    """tests/golden/make_v6_golden.v6_l3 over n frames at once (frames: n x stride bytes, stride >= 24): True where the
+    inner ethertype, behind up to two VLAN tags under XSK_GPU_OPT_VLAN, none cut by the frame's end, is 0x86DD."""
+    be = lambda i: (frames[:, i].astype(np.uint32) << 8) | frames[:, i + 1]  # noqa: E731
+    lens = lens.astype(np.int64)
+    alive = lens >= 14
+    et = be(12)
+    for l3 in ((14, 18) if opts & X.OPT_VLAN else ()):  # (untagged at 14: untagged at 18)
+        tagged = alive & ((et == 0x8100) | (et == 0x88A8))
+        alive &= ~(tagged & (lens < l3 + 4))
+        et = np.where(tagged & alive, be(l3 + 2), et)
+    return alive & (et == 0x86DD)
+
+
+@pytest.mark.parametrize("opts", [0, 7, 0x17])
+def test_indirect_piece_rule(opts):
     """A bound of 4 rounds per workgroup plus one tile runs as consecutive launches, each taking its slice of the count:
-    64-B frames at a 64-B stride against the C oracle, with the count at the bound and in the middle piece."""
+    64-B frames at a 64-B stride against the C oracle, with the count at the bound and in the middle piece; in
+    reference mode, in wire mode and on the dual-stack kernel (0x17: IPv4 traffic only, the generator's 0x86DD frames
+    emptied to len 0, so that the C oracle's wire mode is the reference)."""
+    from tests.v6_frames import G6
     dev = _dev()
     ncu = torch.cuda.get_device_properties(dev).multi_processor_count
     n_max = ncu * 32 * 64 * 4 + 64
     thr = oracle.cpu_threads()
     umem = np.zeros(n_max * 64, np.uint8)
     descs = oracle.synth_batch(umem, n_max, 0, 64, seed=0x5EED71EC, mode=1, len_lo=64, len_hi=64, threads=thr)
+    if opts & 0x10:
+        six = six_mask(umem.reshape(n_max, 64), descs["len"], opts)
+        for i in range(0, n_max, 509):  # the vectorised rule is the spec's, on a sample and on every frame it found
+            f = umem[i * 64:i * 64 + 64].tobytes()
+            assert bool(six[i]) == (G6.v6_l3(f, int(descs[i]["len"]), opts) is not None)
+        for i in np.nonzero(six)[0][:2000]:
+            assert G6.v6_l3(umem[i * 64:i * 64 + 64].tobytes(), int(descs[i]["len"]), opts) is not None
+        descs["len"][six] = 0
     assert (descs["addr"] == np.arange(n_max, dtype=np.uint64) * 64).all() and (descs["len"] <= 64).all()
     after = umem.copy()
-    v_ref, r_ref, _ = oracle.echo_batch(after, descs, threads=thr)
+    if opts:
+        v_ref, r_ref, _ = oracle.echo_batch_opts(after, descs, opts & 7, threads=thr)
+    else:
+        v_ref, r_ref, _ = oracle.echo_batch(after, descs, threads=thr)
     r_ref = r_ref.view(np.uint8).reshape(-1, 16)
     d_orig, d_after, d_descs = to_dev(umem), to_dev(after), to_dev(descs)
     d_v, d_r = to_dev(v_ref), to_dev(r_ref)
@@ -126,7 +155,7 @@ def test_indirect_piece_rule():
         stats = torch.zeros(40, dtype=torch.uint8, device=dev)
         cnt = torch.zeros(1, dtype=torch.int32, device=dev)
         cnt.fill_(count)
-        X.echo_dev_indirect(d_umem, d_descs, cnt, n_max, verd, recs, stats, opts=0)
+        X.echo_dev_indirect(d_umem, d_descs, cnt, n_max, verd, recs, stats, opts=opts)
         torch.cuda.synchronize()
         same_dev(d_umem[:count * 64], d_after[:count * 64], "frames below n")
         same_dev(d_umem[count * 64:], d_orig[count * 64:], "frames at or above n")

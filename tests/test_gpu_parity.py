@@ -664,18 +664,17 @@ def test_more_tiles_than_grid():
     assert torch.equal(before, d_umem)
 
 
-@pytest.mark.parametrize("mode,lo,hi,opts", [(1, 20, 1500, 0), (0, 1500, 1500, 0), (1, 20, 1500, 7), (0, 1500, 1500, 7),
-                                             (1, 20, 1500, 0x17), (0, 1500, 1500, 0x17)])
-def test_tile_spanning_more_than_2gib(mode, lo, hi, opts):
-    """Frames of one tile more than 2 GiB apart (the kernel's 64-bit-address path): ragged tiles take the
-    sorted streams, uniform 1500-B tiles the per-step streams; reference mode, wire mode and the dual-stack kernel
-    (0x17: IPv4 traffic only, so the C oracle's wire mode is the reference; the mixed generator's 0x86DD frames
-    are emptied to len 0, as in test_v6_ipv4_traffic_equals_the_oracle)."""
-    from tests.stream_paths import sub_tile_live, tile_paths
+FAR_SIZE = (2 << 30) + (512 << 20)  # 2.5 GiB UMEM
+FAR_GAP = (2 << 30) + (64 << 20)    # the odd frames lie this far above the even ones
+FAR_N = 200
+
+
+def far_tile_descs(mode, lo, hi, opts):
+    """(frame bytes at a 2048-B stride, descriptors) of FAR_N generator frames (oracle.synth_batch: mode 1 ragged,
+    mode 0 equal lengths) placed alternately below and above a 2 GiB gap; under XSK_GPU_OPT_IPV6 the generator's 0x86DD
+    frames are emptied to len 0 (IPv4 traffic only, so the C oracle's wire mode is the reference).  No GPU needed."""
     from tests.v6_frames import G6
-    size = (2 << 30) + (512 << 20)  # 2.5 GiB UMEM
-    far = (2 << 30) + (64 << 20)
-    n = 200
+    n = FAR_N
     tmp = np.zeros(n * 2048, np.uint8)
     src = oracle.synth_batch(tmp, n, 0, 2048, seed=0x5EED1212, mode=mode, len_lo=lo, len_hi=hi)
     if opts & 0x10:
@@ -684,35 +683,58 @@ def test_tile_spanning_more_than_2gib(mode, lo, hi, opts):
                 src[i]["len"] = 0
         assert all(G6.v6_l3(tmp[i * 2048:(i + 1) * 2048].tobytes(), int(src[i]["len"]), opts) is None for i in range(n))
     far_descs = np.zeros(n, X.DESC_DTYPE)
-    far_descs["addr"] = [(far if i % 2 else 0) + i * 2048 + (i % 5) for i in range(n)]
+    far_descs["addr"] = [(FAR_GAP if i % 2 else 0) + i * 2048 + (i % 5) for i in range(n)]
     far_descs["len"] = src["len"]
-    # (200 frames: the sub-tile kernel, 4-frame tiles, each with frames on both sides of the 2 GiB gap)
-    assert ("sorted_far" if mode else "per_step_far") in tile_paths(far_descs, size, opts != 0, sub_tile_live(n, 0))
+    return tmp, far_descs
+
+
+def far_tile_setup(mode, lo, hi, opts):
+    """far_tile_descs on the device: (UMEM tensor of FAR_SIZE bytes, descriptors, compact host image, its descriptors).
+    The image holds both regions' first FAR_N * 2048 + 64 bytes one after the other, as they are before the transform,
+    and its descriptors the same relative layout: the oracle runs on it."""
+    n, far = FAR_N, FAR_GAP
+    tmp, descs = far_tile_descs(mode, lo, hi, opts)
     dev = _dev()
-    d_umem = torch.zeros(size, dtype=torch.uint8, device=dev)
-    descs = np.zeros(n, X.DESC_DTYPE)
+    d_umem = torch.zeros(FAR_SIZE, dtype=torch.uint8, device=dev)
     for i in range(n):
         a = (far if i % 2 else 0) + i * 2048 + (i % 5)
+        assert a == int(descs[i]["addr"])
         d_umem[a:a + 2048] = torch.from_numpy(tmp[i * 2048:(i + 1) * 2048]).to(dev)
-        descs[i] = (a, src[i]["len"], 0)
-    d_descs = to_dev(descs)
     lo_before = d_umem[:n * 2048 + 64].cpu().numpy().copy()
     hi_before = d_umem[far:far + n * 2048 + 64].cpu().numpy().copy()
-    verd = torch.zeros(n, dtype=torch.uint8, device=dev)
-    recs = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
-    X.echo_dev(d_umem, d_descs, n, verd, recs, opts=opts)
-    torch.cuda.synchronize()
     # oracle on a compact host image: both regions, same relative layout
     img = np.zeros(2 * (n * 2048 + 64), np.uint8)
     img[:n * 2048 + 64] = lo_before
     img[n * 2048 + 64:] = hi_before
     hd = descs.copy()
     hd["addr"] = np.where(np.arange(n) % 2 == 1, descs["addr"] - far + n * 2048 + 64, descs["addr"])
+    return d_umem, descs, img, hd
+
+
+@pytest.mark.parametrize("mode,lo,hi,opts", [(1, 20, 1500, 0), (0, 1500, 1500, 0), (1, 20, 1500, 7), (0, 1500, 1500, 7),
+                                             (1, 20, 1500, 0x17), (0, 1500, 1500, 0x17)])
+def test_tile_spanning_more_than_2gib(mode, lo, hi, opts):
+    """Frames of one tile more than 2 GiB apart (the kernel's 64-bit-address path): ragged tiles take the
+    sorted streams, uniform 1500-B tiles the per-step streams; reference mode, wire mode and the dual-stack kernel
+    (0x17: IPv4 traffic only, so the C oracle's wire mode is the reference; the mixed generator's 0x86DD frames
+    are emptied to len 0, as in test_v6_ipv4_traffic_equals_the_oracle)."""
+    from tests.stream_paths import sub_tile_live, tile_paths
+    n = FAR_N
+    far_descs = far_tile_descs(mode, lo, hi, opts)[1]
+    # (200 frames: the sub-tile kernel, 4-frame tiles, each with frames on both sides of the 2 GiB gap)
+    assert ("sorted_far" if mode else "per_step_far") in tile_paths(far_descs, FAR_SIZE, opts != 0, sub_tile_live(n, 0))
+    dev = _dev()
+    d_umem, descs, img, hd = far_tile_setup(mode, lo, hi, opts)
+    d_descs = to_dev(descs)
+    verd = torch.zeros(n, dtype=torch.uint8, device=dev)
+    recs = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    X.echo_dev(d_umem, d_descs, n, verd, recs, opts=opts)
+    torch.cuda.synchronize()
     v_ref, r_ref, _ = oracle.echo_batch_opts(img, hd, opts & 7)
     assert (verd.cpu().numpy() == v_ref).all()
     assert (recs.cpu().numpy().view(X.REC_DTYPE) == r_ref).all()
     assert (d_umem[:n * 2048 + 64].cpu().numpy() == img[:n * 2048 + 64]).all()
-    assert (d_umem[far:far + n * 2048 + 64].cpu().numpy() == img[n * 2048 + 64:]).all()
+    assert (d_umem[FAR_GAP:FAR_GAP + n * 2048 + 64].cpu().numpy() == img[n * 2048 + 64:]).all()
 
 
 def test_write_through_across_4gib_regions():

@@ -126,6 +126,121 @@ def test_long_batches_take_their_paths(v6):
     assert len({(o + ln + 255) >> 8 for ln, o, _ in tile}) > 32 and min((o + ln) >> 8 for ln, o, _ in tile) > 7
 
 
+# ---- the resident kernels' tiling, restated ------------------------------------------------------------------------
+def test_resident_slices_and_groups():
+    """Literal values worked out from xsk_gpu__ll_slice / xsk_gpu__ll_groups (xsk_lowlat_proto.h); the group cases are
+    those of tests/c/test_lowlat_proto.c, step 10."""
+    assert [S.ll_slice(1024, 4, g) for g in range(4)] == [(0, 256), (256, 512), (512, 768), (768, 1024)]
+    assert [S.ll_slice(1023, 4, g) for g in range(4)] == [(0, 256), (256, 512), (512, 768), (768, 1023)]
+    assert [S.ll_slice(65, 4, g) for g in range(4)] == [(0, 20), (20, 40), (40, 60), (60, 65)]  # per = 17 -> 20
+    assert [S.ll_slice(5, 4, g) for g in range(4)] == [(0, 4), (4, 5), (5, 5), (5, 5)]
+    assert S.ll_slice(64, 1, 0) == (0, 64)
+    for n in (1, 3, 64, 65, 127, 1000, 1024):  # as step 9 there: contiguous, multiples of 4 but the last, covering
+        for w in range(1, S.LL_WG + 1):
+            sl = [S.ll_slice(n, w, g) for g in range(w)]
+            assert sl[0][0] == 0 and sl[-1][1] == n and all(a[1] == b[0] for a, b in zip(sl, sl[1:]))
+            assert all((f1 - f0) % 4 == 0 for f0, f1 in sl if f1 < n)
+    d = descs_of(tile_at(1500, n=1024))
+    assert S.ll_groups(d[:64]) == 1 and S.ll_groups(d[:65]) == 4 and S.ll_groups(d[:100]) == 4 and S.ll_groups(d) == 4
+    d = descs_of(tile_at(64, n=1024))
+    assert S.ll_groups(d[:128]) == 1 and S.ll_groups(d[:129]) == 4              # 8 KiB; more than 128 frames
+    assert S.ll_groups(d[:300]) == 4 and S.ll_groups(d[:256]) == 4
+    d[0]["len"] = 1500
+    assert S.ll_groups(d[:128]) == 1                                            # 9.5 KiB
+    d[:16]["len"] = 1500
+    assert S.ll_groups(d[:128]) == 4                                            # 30 KiB
+    # the 128-frame / 16 KiB line itself, and a frame counted up to 4096 B only
+    d = descs_of(tile_at(128, n=128))
+    assert int(d["len"].sum()) == 16 << 10 and S.ll_groups(d) == 1
+    d[77]["len"] = 129
+    assert S.ll_groups(d) == 4
+    d = descs_of(tile_at(64, n=128))
+    d[:2]["len"] = 1 << 20                                                      # 2 x 4096 + 126 x 64 = 16 256
+    assert S.ll_groups(d) == 1
+    d[2]["len"] = 1 << 20                                                       # 20 288
+    assert S.ll_groups(d) == 4
+
+
+def test_resident_tile_size():
+    """xsk_gpu__small_tile (xsk_gpu_internal.h) of slice 0, one size for every slice; the tuned values replace it."""
+    assert S.resident_tiling(descs_of(tile_at(64, n=64))) == (64, [(0, 64)])      # 4 KiB: one wave, one 64-frame tile
+    assert S.resident_tiling(descs_of(tile_at(98, n=64))) == (64, [(0, 64)])      # 6.1 KiB: the RX loop's 64 pings
+    assert S.resident_tiling(descs_of(tile_at(1500, n=1024))) == \
+        (16, [(0, 256), (256, 512), (512, 768), (768, 1024)])                     # 375 KiB a slice: 16 waves of 16
+    assert S.resident_tiling(descs_of(tile_at(1500, n=64))) == (8, [(0, 64)])     # 93.75 KiB: 12 waves, 6 -> 8 frames
+    assert S.resident_tiling(descs_of(tile_at(98, n=1024)))[0] == 64              # 24.5 KiB a slice: 4 waves of 64
+    assert S.resident_tiling(descs_of(tile_at(128, n=128))) == (64, [(0, 128)])   # 16 KiB on the leader: 2 waves
+    assert S.resident_tiling(descs_of(tile_at(1500, n=1))) == (4, [(0, 1)])
+    assert S.resident_tiling(descs_of(tile_at(1 << 20, n=64, stride=1 << 21))) == (4, [(0, 64)])  # 4 KiB each
+    # slice 0 decides: 256 frames of 64 B (2 waves: 64 a tile) in front of 768 of 1500 B
+    d = descs_of(tile_at(1500, n=1024))
+    d[:256]["len"] = 64
+    assert S.resident_tiling(d)[0] == 64
+    # tuned (xsk_gpu__lowlat_tune): min(groups, n) workgroups, tile_frames a tile
+    d = descs_of(tile_at(1500, n=1024))
+    assert S.resident_tiling(d, groups=1, tile_frames=64) == (64, [(0, 1024)])
+    assert S.resident_tiling(d, groups=2) == (32, [(0, 512), (512, 1024)])        # 750 KiB: 16 waves of 32
+    assert S.resident_tiling(d[:2], groups=4) == (4, [(0, 2), (2, 2)])            # the second slice empty
+    assert S.resident_tiling(d[:64], tile_frames=4) == (4, [(0, 64)])
+    # tiles start at their slice's first frame: 65 frames of 1500 B, 4 slices of 20 / 20 / 20 / 5 frames; slice 0 is
+    # 29.3 KiB, 4 waves, ceil(20 / 4) = 5 -> 8 frames a tile: tiles of 8, 8, 4 frames per full slice, one of 5
+    assert S.resident_tiling(d[:65]) == (8, [(0, 20), (20, 40), (40, 60), (60, 65)])
+    assert S.resident_tile_paths(d[:65], SIZE, False) == ["per_step"] * 10
+    d2 = d[:65].copy()
+    d2[16:20]["len"] = 60  # the third tile of slice 0, and no part of a tile of slice 1
+    assert S.resident_tile_paths(d2, SIZE, False) == ["per_step"] * 2 + ["short"] + ["per_step"] * 7
+    assert S.resident_tile_paths(d[:64], SIZE, False, tile_frames=64) == ["uniform"]
+    assert S.resident_tile_paths(d[:64], SIZE, False) == ["per_step"] * 8
+
+
+@pytest.mark.parametrize("v6", [False, True])
+def test_resident_path_tables(v6):
+    """The resident-kernel matrix's three batches of every case take the paths of S.resident_table, in reference and in
+    wire mode, and their union is the six ordinary paths."""
+    for wire in (False, True):
+        reached = {name: set() for name, *_ in S.RESIDENT_GEOMETRIES}
+        for shape in S.SHAPES:
+            want = S.resident_table(shape, v6)
+            for off in S.SHAPE_OFFS[shape]:
+                umem, descs, path = S.shape_batch(shape, v6, off, 1105)
+                for name, n, groups, tile in S.RESIDENT_GEOMETRIES:
+                    got = S.resident_tile_paths(descs[:n], umem.nbytes, wire, groups, tile)
+                    assert {p: got.count(p) for p in set(got)} == want[name], (shape, off, wire, name, got)
+                    reached[name] |= set(got)
+                    if name == "tuned":  # whole 64-frame tiles: the shape's own path on the plain tiles
+                        assert got[0] == got[1] == path
+        assert reached["full"] == reached["poll"] == {"mid_uni", "mid", "short", "per_step", "sorted"}, reached
+        assert reached["tuned"] == {"mid_uni", "mid", "short", "uniform", "per_step", "sorted"}, reached
+
+
+@pytest.mark.parametrize("v6", [False, True])
+def test_indirect_counts_reach_every_ordinary_path(v6):
+    """The indirect-kernel matrix (tests/test_gpu_indirect_paths.py: counts 1105 and 100 of every case's 1105-frame
+    batch): the full count keeps the shape's path on tiles 0 and 1; count 100 keeps it on tile 0 and cuts tile 1 at
+    36 live frames, which turns `uniform` into `per_step` and `mid_uni` into `mid`; every ordinary path is reached in
+    both modes."""
+    for wire in (False, True):
+        reached = set()
+        for shape in S.SHAPES:
+            for off in S.SHAPE_OFFS[shape]:
+                umem, descs, path = S.shape_batch(shape, v6, off, 1105)
+                full = S.tile_paths(descs, umem.nbytes, wire)
+                cut = S.tile_paths(descs[:100], umem.nbytes, wire)
+                assert len(full) == 18 and full[0] == full[1] == path and full[17] != "none"
+                assert cut == [path, {"uniform": "per_step", "mid_uni": "mid"}.get(path, path)], (shape, off, cut)
+                reached |= set(full) | set(cut)
+        assert reached == {"mid_uni", "mid", "short", "uniform", "per_step", "sorted"}, reached
+
+
+@pytest.mark.parametrize("v6", [False, True])
+def test_indirect_long_batches_take_their_paths(v6):
+    for name, (tiles, n, want) in S.INDIRECT_LONG_BATCHES.items():
+        umem, descs = S.long_batch(v6, tiles(), n)
+        assert umem.nbytes <= 40 * MIB
+        for wire in (False, True):
+            assert S.tile_paths(descs, umem.nbytes, wire) == want, name
+
+
 # ---- the references alone are right on long frames -----------------------------------------------------------------
 def big_csum16(data: bytes) -> int:
     """RFC 1071 by one big integer: the sum of the 16-bit big-endian words is the number's digit sum in base 65536,
