@@ -475,6 +475,71 @@ int xsk_gpu_ingress_dev_opts(void* d_umem, uint64_t umem_size, const struct xsk_
                              uint32_t* d_nout, uint8_t* d_verdicts, struct xsk_gpu_rec* d_recs,
                              struct xsk_gpu_stats* d_stats, void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Egress on the device (build-added): the step handle_receive_packets() takes behind         */
+/* process_packet() -- every TX_REPLY frame onto the TX ring, as many as it has room for,      */
+/* every other frame back to the free-frame pool, the tx counters corrected for replies that   */
+/* found the ring full (xsk_receive.c:174-186, 226-227) -- over a device-resident batch.  The  */
+/* host modes do it in xsk_gpu_rx_step() (step 4); xsk_gpu_egress_dev() turns (descriptors,    */
+/* verdicts) into the TX descriptor list, the free-frame address list and their counts, all in */
+/* device memory, exactly as that sequential loop produces them.                               */
+/*   d_descs, d_verdicts : n_max descriptors (16-B aligned) and n_max verdict bytes (any       */
+/*                         alignment), e.g. d_out and d_verdicts of xsk_gpu_ingress_dev_opts() */
+/*   d_n        : one uint32_t in device memory (4-B aligned), or NULL.  n = d_n ? min(*d_n,   */
+/*                n_max) : n_max; the word is read when the kernels EXECUTE, as in             */
+/*                xsk_gpu_echo_dev_indirect(): stream-ordered after whatever wrote it          */
+/*   d_tx_room  : one uint32_t in device memory (4-B aligned), or NULL: the free slots of the  */
+/*                caller's TX ring, read like *d_n (a graph replay may change it).             */
+/*                room = d_tx_room ? *d_tx_room : UINT32_MAX                                   */
+/*   d_tx       : room for min(n_max, room) descriptors (16-B aligned)                         */
+/*   d_free     : room for n_max uint64_t UMEM offsets (8-B aligned): what the fill ring and   */
+/*                struct xsk_gpu_frame_pool hold                                               */
+/*   d_counts   : one struct xsk_gpu_egress_counts (4-B aligned)                               */
+/*   d_stats    : one xsk_gpu_stats in device memory (8-B aligned), the one the transform      */
+/*                accumulated into; or NULL                                                    */
+/*   d_workspace: xsk_gpu_egress_workspace_size(n_max) bytes of device memory; may be NULL iff */
+/*                n_max <= XSK_GPU_LOWLAT_MAX                                                  */
+/* Per frame i < n: reply(i) = (d_verdicts[i] == XSK_GPU_TX_REPLY), every other byte value is  */
+/* "not a reply"; R(i) = the number of replies at indices below i, R = R(n).                   */
+/*   A reply with R(i) < room is submitted: d_tx[R(i)] = { d_descs[i].addr, d_descs[i].len, 0 } */
+/*        (options is written as 0, as xsk_gpu_rx_step() writes it; it is not copied).         */
+/*   Every other frame is freed: d_free[i - min(R(i), room)] = d_descs[i].addr -- the          */
+/*        non-replies and the replies past the room.                                           */
+/* Both lists are in batch order.                                                              */
+/*   *d_counts = { n, n_tx = min(R, room), n_tx_full = R - n_tx, n_free = n - n_tx }.          */
+/*   d_stats: tx_packets -= n_tx_full, tx_bytes -= the summed len of the replies not           */
+/*        submitted, so that the counters count frames actually submitted, as                  */
+/*        xsk_gpu_rx_step() documents.  Device-scope 64-bit atomics; none when n_tx_full == 0. */
+/* Not written: d_tx[k] for k >= n_tx, d_free[k] for k >= n_free.  No descriptor or verdict at */
+/* an index >= n is read.  n == 0 with n_max > 0 writes zero counts and nothing else.          */
+/* Checked before any device call, -EINVAL: d_descs, d_tx NULL or not 16-B aligned; d_free     */
+/* NULL or not 8-B aligned; d_counts NULL or not 4-B aligned; d_n, d_tx_room not 4-B aligned;  */
+/* d_stats not 8-B aligned; d_verdicts NULL; n_max > XSK_GPU_MAX_BATCH; d_workspace NULL with  */
+/* n_max > XSK_GPU_LOWLAT_MAX; d_tx == d_descs (the outputs may not overlap the inputs; this   */
+/* is the one case the call refuses itself).                                                   */
+/* n_max == 0 sets *d_counts to zero with an asynchronous memset and launches nothing.         */
+/* Asynchronous on `stream`; allocates nothing, synchronises nothing and reads no device       */
+/* memory from the host, so a stream under graph capture may contain it (behind                */
+/* xsk_gpu_ingress_dev_opts(), with d_n = its d_nout).                                         */
+/* Kernels (xsk_egress.hip): n_max <= XSK_GPU_LOWLAT_MAX is one launch of one workgroup; a     */
+/* larger bound is three launches (per-workgroup reply counts, one scan, the scatter), as the  */
+/* filter's compaction.                                                                        */
+/* ------------------------------------------------------------------------------------------ */
+struct xsk_gpu_egress_counts {
+    uint32_t n;         /* frames served: min(*d_n, n_max)                  */
+    uint32_t n_tx;      /* entries of d_tx: replies submitted               */
+    uint32_t n_tx_full; /* replies freed because the ring had no room left  */
+    uint32_t n_free;    /* entries of d_free                                */
+};
+
+/* Bytes of device workspace xsk_gpu_egress_dev() needs for a bound of n_max frames (0 up to XSK_GPU_LOWLAT_MAX). */
+size_t xsk_gpu_egress_workspace_size(uint32_t n_max);
+
+int xsk_gpu_egress_dev(const struct xsk_gpu_desc* d_descs, const uint8_t* d_verdicts, const uint32_t* d_n,
+                       uint32_t n_max, const uint32_t* d_tx_room, struct xsk_gpu_desc* d_tx, uint64_t* d_free,
+                       struct xsk_gpu_egress_counts* d_counts, struct xsk_gpu_stats* d_stats, void* d_workspace,
+                       void* stream);
+
 /* The UMEM allocation for the host modes: the reference allocates its UMEM with posix_memalign(getpagesize(),
  * NUM_FRAMES * FRAME_SIZE) (src/lib/xsk_utils.c:132-135); this gives the same kind of memory (anonymous, private,
  * page-aligned: AF_XDP registers it as it is) 2 MiB aligned, advised onto transparent huge pages and touched up front.

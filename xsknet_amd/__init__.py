@@ -27,6 +27,7 @@ __all__ = [
     "classify_dev", "XDP_DROP", "XDP_PASS", "XDP_REDIRECT", "DROP_BAD_IP", "DROP_BAD_CSUM",
     "OPT_STRICT_IPV4", "OPT_VLAN", "OPT_VERIFY_CSUM", "OPT_ALL", "F_IP_CSUM_OK", "F_ICMP_CSUM_OK", "F_VLAN",
     "F_IP_OPTIONS", "OPT_IPV6", "OPT_MASK", "F_IPV6",
+    "egress_dev", "egress_workspace_size", "EGRESS_COUNTS_DTYPE",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,7 +60,10 @@ REC_DTYPE = np.dtype([
 # struct xsk_gpu_stats == struct stats_record (xsk_utils.h:17-23)
 STATS_DTYPE = np.dtype([("timestamp", "<u8"), ("rx_packets", "<u8"), ("rx_bytes", "<u8"),
                         ("tx_packets", "<u8"), ("tx_bytes", "<u8")])
+# struct xsk_gpu_egress_counts (16 B, device memory): what egress_dev leaves beside its two lists
+EGRESS_COUNTS_DTYPE = np.dtype([("n", "<u4"), ("n_tx", "<u4"), ("n_tx_full", "<u4"), ("n_free", "<u4")])
 assert DESC_DTYPE.itemsize == 16 and REC_DTYPE.itemsize == 16 and STATS_DTYPE.itemsize == 40
+assert EGRESS_COUNTS_DTYPE.itemsize == 16
 
 
 class XskGpuError(RuntimeError):
@@ -104,6 +108,8 @@ _SIGS = {
     "xsk_gpu_echo_dev_indirect": ([_P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_ingress_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P],
                                  C.c_int),
+    "xsk_gpu_egress_workspace_size": ([C.c_uint32], C.c_size_t),
+    "xsk_gpu_egress_dev": ([_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_set_options": ([_P, C.c_uint32], C.c_int),
     "xsk_gpu_init": ([C.POINTER(_P), C.c_int, _P, C.c_uint64, C.c_uint32, C.c_int], C.c_int),
     "xsk_gpu_process": ([_P, _P, C.c_uint32, _P, _P, _P], C.c_int),
@@ -282,6 +288,28 @@ def ingress_dev(umem, descs, n: int, bound: bool, actions, out, nout, verdicts=N
     _check("xsk_gpu_ingress_dev_opts", lib().xsk_gpu_ingress_dev_opts(
         _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, opts, 1 if bound else 0, _ptr(actions),
         _ptr(out), _ptr(nout), _ptr(verdicts), _ptr(recs), _ptr(stats), _ptr(workspace), _stream_ptr(stream)))
+
+
+def egress_workspace_size(n_max: int) -> int:
+    """xsk_gpu_egress_workspace_size: bytes of device workspace egress_dev needs for a bound of n_max frames (0 up to
+    LOWLAT_MAX)."""
+    return int(lib().xsk_gpu_egress_workspace_size(n_max))
+
+
+def egress_dev(descs, verdicts, n_max: int, tx, free, counts, count=None, tx_room=None, stats=None, workspace=None,
+               stream=None) -> None:
+    """xsk_gpu_egress_dev: (descriptors, verdicts) -> the TX descriptor list `tx`, the free-frame address list `free`
+    (uint64 UMEM offsets) and `counts` (one EGRESS_COUNTS_DTYPE), all on the device, as xsk_gpu_rx_step's step 4 builds
+    them.  `count` and `tx_room` are uint32 words on the device (int32 tensors of one element) that the kernels read
+    when they execute: the frame count (None = n_max) and the TX ring's free slots (None = unlimited).  Behind
+    ingress_dev: descs=out, count=nout.  Inside a graph capture pass `workspace` (egress_workspace_size bytes) when
+    n_max > LOWLAT_MAX: allocating it here would be part of the capture."""
+    if workspace is None and n_max > LOWLAT_MAX:
+        import torch
+        workspace = torch.empty(egress_workspace_size(n_max), dtype=torch.uint8, device=descs.device)
+    _check("xsk_gpu_egress_dev", lib().xsk_gpu_egress_dev(
+        _ptr(descs), _ptr(verdicts), _ptr(count), n_max, _ptr(tx_room), _ptr(tx), _ptr(free), _ptr(counts),
+        _ptr(stats), _ptr(workspace), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,
