@@ -476,6 +476,128 @@ int xsk_gpu_ingress_dev_opts(void* d_umem, uint64_t umem_size, const struct xsk_
                              struct xsk_gpu_stats* d_stats, void* d_workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Steering (build-added): the ingress filter in front of up to 64 sockets.  Both XDP programs */
+/* of the reference redirect through a 64-entry map -- an xsks_map looked up by RX queue       */
+/* (src/kern/inner_xdp.c:11-16,57-58), an xdp_devmap meant to "redirect packets to different   */
+/* virtual interfaces depending on the port number" whose key the code leaves at a constant 0  */
+/* (src/kern/phy_xdp.c:8-12,31-36,67-80).  xsk_gpu_classify_dev[_opts]() collapses that map to */
+/* one bit, target_bound; xsk_gpu_steer_dev() keeps it: a REDIRECT frame goes to a port, the   */
+/* port is looked up by the frame's IP destination address, and the REDIRECT descriptors come  */
+/* out grouped by port.  Frames to an address the table does not hold can be left to the       */
+/* kernel stack (default_port == XSK_GPU_STEER_PASS): an echo request to a broadcast or        */
+/* multicast address is then not answered with that address as the reply's source.             */
+/*                                                                                              */
+/* The table: n_entries <= XSK_GPU_STEER_MAX_ENTRIES entries in device memory (8-B aligned),    */
+/* strictly ascending by the 17 bytes (family, addr[0..16)) as memcmp orders them, which is     */
+/* how xsk_gpu_steer_table_prepare() leaves a host array.  The device calls cannot check a      */
+/* table in device memory without a synchronisation, so they do not: a table that was not       */
+/* prepared (unsorted, duplicate keys, a family other than 4 or 6, nonzero tail bytes) may miss */
+/* matches -- a frame then takes default_port, or an entry's port >= n_ports drops it -- but it */
+/* never causes a read outside d_table[0, n_entries).                                           */
+/*                                                                                              */
+/* Per frame: the action is decided as by xsk_gpu_classify_dev() for opts == 0 and as by rules  */
+/* 1-6 of xsk_gpu_classify_dev_opts() for nonzero opts (opts & ~XSK_GPU_OPT_MASK is -EINVAL),   */
+/* except at the point where those rules say REDIRECT.  There, with l3 where the rules found    */
+/* the IP header (14 for opts == 0):                                                            */
+/*   1. dst = bytes [l3 + 16, l3 + 20) with family 4, or [l3 + 24, l3 + 40) with family 6.      */
+/*      Both ranges lie inside [addr, addr + len) by the rules already passed (len >= l3 + 20,  */
+/*      len >= l3 + 40; opts == 0: len >= 34 and the first 34 bytes inside the UMEM), so the    */
+/*      read bound of the filter stays as it is: only bytes of [addr, addr + len);              */
+/*   2. port = the port of the table entry whose key is (family, dst) -- a family-4 key is the  */
+/*      four address bytes followed by twelve zeros -- if there is one, else default_port;      */
+/*   3. port == XSK_GPU_STEER_PASS: XSK_GPU_XDP_PASS, the frame is not ours;                    */
+/*   4. otherwise port >= n_ports, or bit `port` of *d_bound clear: XSK_GPU_XDP_DROP, the       */
+/*      reference's "no entry in the map" (inner_xdp.c:60, phy_xdp.c:71-73);                    */
+/*   5. otherwise XSK_GPU_XDP_REDIRECT to `port`.                                               */
+/* An IPv6 frame whose destination is the last sixteen bytes of the frame (len == l3 + 40) is   */
+/* never looked up: rule 5 of the filter drops it for its cut ICMPv6 header (or passes it for   */
+/* its next header) first.                                                                      */
+/*   d_table, n_entries : as above; d_table may be NULL iff n_entries == 0.  Read when the      */
+/*                        kernels EXECUTE (a graph replay sees entries overwritten in place)    */
+/*   default_port       : below n_ports, or XSK_GPU_STEER_PASS                                  */
+/*   n_ports            : 1 .. XSK_GPU_STEER_MAX_PORTS                                          */
+/*   d_bound            : one uint64_t in device memory (8-B aligned), bit p set = port p is    */
+/*                        bound; read when the kernels execute, like *d_tx_room of              */
+/*                        xsk_gpu_egress_dev() (a graph replay may bind and unbind ports).      */
+/*                        NULL: every port below n_ports is bound                               */
+/*   d_actions          : n bytes: the action of frame i                                        */
+/*   d_ports            : n bytes, required: the port of a REDIRECT frame, XSK_GPU_STEER_PASS   */
+/*                        for every other frame                                                 */
+/*   d_out              : room for n descriptors (16-B aligned): the REDIRECT descriptors       */
+/*                        grouped by ascending port, each group in batch order (a stable        */
+/*                        partition).  Entries at or above the total are not written            */
+/*   d_off              : n_ports + 1 words (4-B aligned): port p's list is                     */
+/*                        d_out[d_off[p], d_off[p + 1]), d_off[0] == 0, d_off[n_ports] is the   */
+/*                        total.  d_out and d_off are required together or both NULL (actions   */
+/*                        and ports only), as d_out / d_nout of the filter                      */
+/*   d_workspace        : xsk_gpu_steer_workspace_size(n, n_ports) bytes, zero or garbage       */
+/* Checked before any device call, -EINVAL: the rules of xsk_gpu_classify_dev_opts() (here for  */
+/* every n, 0 included); n_ports outside [1, 64]; default_port neither below n_ports nor        */
+/* XSK_GPU_STEER_PASS; n_entries > XSK_GPU_STEER_MAX_ENTRIES; n_entries > 0 with d_table NULL   */
+/* or not 8-B aligned; d_bound not 8-B aligned; d_off not 4-B aligned; d_ports NULL; one of     */
+/* d_out / d_off without the other.  n == 0 zeroes d_off (when given) with an asynchronous      */
+/* memset and launches nothing.                                                                 */
+/* Identity: with n_entries == 0, default_port == 0, n_ports == 1 and *d_bound == (target_bound */
+/* != 0), d_actions and d_out are exactly those of xsk_gpu_classify_dev_opts(opts,              */
+/* target_bound) for every option word, 0 included, and d_off[1] == *d_nout.                    */
+/* Asynchronous on `stream`; allocates nothing, synchronises nothing and reads no device memory */
+/* from the host, so a stream under graph capture may contain it.                               */
+/* Kernels (xsk_steer.hip), three launches as the filter's compaction: classify (a lane per     */
+/* frame; the table staged once per workgroup into LDS and searched there; per-workgroup,       */
+/* per-port counts), the exclusive scan of the n_ports x workgroups count matrix (a workgroup   */
+/* per port), the scatter (wave ballots per distinct port: no atomics, so batch order holds;    */
+/* it also writes d_off).  Without d_out only the first.                                        */
+/* ------------------------------------------------------------------------------------------ */
+#define XSK_GPU_STEER_MAX_PORTS   64u    /* max_entries of the reference's xsks_map / xdp_devmap */
+#define XSK_GPU_STEER_MAX_ENTRIES 1024u
+#define XSK_GPU_STEER_PASS        0xFFu  /* "no port": the frame is left to the kernel stack */
+
+struct xsk_gpu_steer_entry {   /* 24 bytes */
+    uint8_t addr[16];          /* family 4: addr[0..4) in network order, addr[4..16) zero; family 6: all 16 */
+    uint8_t family;            /* 4 or 6 */
+    uint8_t port;              /* < XSK_GPU_STEER_MAX_PORTS */
+    uint8_t pad[6];            /* zero */
+};
+
+/* Host only, no device call: check n entries in host memory and sort them in place, strictly ascending by (family,
+ * addr[0..16)) as memcmp compares those 17 bytes.  -EINVAL, the array untouched, for n > XSK_GPU_STEER_MAX_ENTRIES,
+ * entries NULL with n > 0, a family other than 4 or 6, a family-4 entry with a nonzero byte in addr[4..16), a port
+ * >= XSK_GPU_STEER_MAX_PORTS, nonzero padding; -EEXIST when two entries have the same key (the array is left sorted).
+ * n == 0 is 0. */
+int xsk_gpu_steer_table_prepare(struct xsk_gpu_steer_entry* entries, uint32_t n);
+
+/* Bytes of zero-or-garbage device workspace xsk_gpu_steer_dev() needs for n frames and n_ports ports: one word per
+ * 256-frame workgroup and port (1 MiB at 2^20 frames and 64 ports). */
+size_t xsk_gpu_steer_workspace_size(uint32_t n, uint32_t n_ports);
+
+int xsk_gpu_steer_dev(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
+                      uint32_t opts, const struct xsk_gpu_steer_entry* d_table, uint32_t n_entries,
+                      uint32_t default_port, uint32_t n_ports, const uint64_t* d_bound,
+                      uint8_t* d_actions, uint8_t* d_ports, struct xsk_gpu_desc* d_out, uint32_t* d_off,
+                      void* d_workspace, void* stream);
+
+/* Steered ingress in one asynchronous call: xsk_gpu_steer_dev(..., d_out, d_off, ...) followed on the same stream by
+ * xsk_gpu_echo_dev_indirect(d_umem, umem_size, d_out, &d_off[n_ports], n, opts, ...).  The groups of d_out are
+ * contiguous, so one transform serves every port; d_verdicts and d_recs (n entries each, or NULL) are indexed by
+ * position in d_out, so port p's verdicts are d_verdicts[d_off[p], d_off[p + 1]), and entries at or above
+ * d_off[n_ports] are not written.  d_out and d_off are required.  All arguments are checked before the first launch
+ * (the rules of both calls; -EINVAL).  The counters, and everything else the comment of xsk_gpu_ingress_dev_opts()
+ * says, carry over with d_off[n_ports] in the place of *d_nout: rx_packets grows by d_off[n_ports] and rx_bytes by the
+ * redirected frames' summed len; for nonzero opts the tx counters and every UMEM byte equal what
+ * xsk_gpu_echo_dev_opts() alone leaves over the frames the steering rule redirects; with nothing bound no frame or
+ * counter changes; and the opts == 0 caveat (frames of 20 to 33 bytes the reference transform would answer stay as
+ * they are behind the reference's filter) holds here too.
+ * Not built: xsk_gpu_egress_dev() takes one list that starts at a pointer the host knows, so it serves the whole of
+ * d_out (every port's replies on one TX list), not port p's segment, whose start is a device word; a segmented egress
+ * is the follow-up.  The host modes are unchanged: there the kernel's XDP program has already chosen the socket. */
+int xsk_gpu_ingress_steer_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
+                              uint32_t opts, const struct xsk_gpu_steer_entry* d_table, uint32_t n_entries,
+                              uint32_t default_port, uint32_t n_ports, const uint64_t* d_bound,
+                              uint8_t* d_actions, uint8_t* d_ports, struct xsk_gpu_desc* d_out, uint32_t* d_off,
+                              uint8_t* d_verdicts, struct xsk_gpu_rec* d_recs, struct xsk_gpu_stats* d_stats,
+                              void* d_workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Egress on the device (build-added): the step handle_receive_packets() takes behind         */
 /* process_packet() -- every TX_REPLY frame onto the TX ring, as many as it has room for,      */
 /* every other frame back to the free-frame pool, the tx counters corrected for replies that   */

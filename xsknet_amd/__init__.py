@@ -28,6 +28,8 @@ __all__ = [
     "OPT_STRICT_IPV4", "OPT_VLAN", "OPT_VERIFY_CSUM", "OPT_ALL", "F_IP_CSUM_OK", "F_ICMP_CSUM_OK", "F_VLAN",
     "F_IP_OPTIONS", "OPT_IPV6", "OPT_MASK", "F_IPV6",
     "egress_dev", "egress_workspace_size", "EGRESS_COUNTS_DTYPE",
+    "STEER_ENTRY_DTYPE", "STEER_PASS", "STEER_MAX_PORTS", "STEER_MAX_ENTRIES", "steer_table_prepare",
+    "steer_workspace_size", "steer_dev", "ingress_steer_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,6 +66,10 @@ STATS_DTYPE = np.dtype([("timestamp", "<u8"), ("rx_packets", "<u8"), ("rx_bytes"
 EGRESS_COUNTS_DTYPE = np.dtype([("n", "<u4"), ("n_tx", "<u4"), ("n_tx_full", "<u4"), ("n_free", "<u4")])
 assert DESC_DTYPE.itemsize == 16 and REC_DTYPE.itemsize == 16 and STATS_DTYPE.itemsize == 40
 assert EGRESS_COUNTS_DTYPE.itemsize == 16
+# struct xsk_gpu_steer_entry (24 B): one row of steer_dev's table, key (family, addr) -> port
+STEER_ENTRY_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("port", "u1"), ("pad", "u1", (6,))])
+STEER_PASS, STEER_MAX_PORTS, STEER_MAX_ENTRIES = 0xFF, 64, 1024  # XSK_GPU_STEER_*
+assert STEER_ENTRY_DTYPE.itemsize == 24
 
 
 class XskGpuError(RuntimeError):
@@ -110,6 +116,12 @@ _SIGS = {
                                  C.c_int),
     "xsk_gpu_egress_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_egress_dev": ([_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_steer_table_prepare": ([_P, C.c_uint32], C.c_int),
+    "xsk_gpu_steer_workspace_size": ([C.c_uint32, C.c_uint32], C.c_size_t),
+    "xsk_gpu_steer_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P,
+                           _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_ingress_steer_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                   _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_set_options": ([_P, C.c_uint32], C.c_int),
     "xsk_gpu_init": ([C.POINTER(_P), C.c_int, _P, C.c_uint64, C.c_uint32, C.c_int], C.c_int),
     "xsk_gpu_process": ([_P, _P, C.c_uint32, _P, _P, _P], C.c_int),
@@ -309,6 +321,52 @@ def egress_dev(descs, verdicts, n_max: int, tx, free, counts, count=None, tx_roo
         workspace = torch.empty(egress_workspace_size(n_max), dtype=torch.uint8, device=descs.device)
     _check("xsk_gpu_egress_dev", lib().xsk_gpu_egress_dev(
         _ptr(descs), _ptr(verdicts), _ptr(count), n_max, _ptr(tx_room), _ptr(tx), _ptr(free), _ptr(counts),
+        _ptr(stats), _ptr(workspace), _stream_ptr(stream)))
+
+
+def steer_table_prepare(entries: np.ndarray) -> np.ndarray:
+    """xsk_gpu_steer_table_prepare on a copy of a host array of STEER_ENTRY_DTYPE: checked and sorted by (family,
+    addr), the order steer_dev's search needs.  Raises XskGpuError (-EINVAL, -EEXIST)."""
+    e = np.array(entries, dtype=STEER_ENTRY_DTYPE, copy=True).reshape(-1)
+    _check("xsk_gpu_steer_table_prepare", lib().xsk_gpu_steer_table_prepare(e.ctypes.data if len(e) else None, len(e)))
+    return e
+
+
+def steer_workspace_size(n: int, n_ports: int) -> int:
+    """xsk_gpu_steer_workspace_size: bytes of device workspace steer_dev needs for n frames and n_ports ports."""
+    return int(lib().xsk_gpu_steer_workspace_size(n, n_ports))
+
+
+def _steer_workspace(umem, n: int, n_ports: int):
+    import torch
+    return torch.empty(max(steer_workspace_size(max(n, 1), n_ports), 4), dtype=torch.uint8, device=umem.device)
+
+
+def steer_dev(umem, descs, n: int, table, n_entries: int, default_port: int, n_ports: int, bound, actions, ports,
+              out=None, off=None, workspace=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_steer_dev: the ingress filter with a port per REDIRECT frame, looked up by destination address in
+    `table` (a device copy of a steer_table_prepare()d array, or None with n_entries == 0), and the REDIRECT
+    descriptors in `out` grouped by port, port p's at out[off[p]:off[p + 1]] (`off`: n_ports + 1 uint32 words).
+    `bound` is a uint64 word on the device (bit p = port p bound; None = all), read when the kernels execute.  Inside a
+    graph capture pass `workspace` (steer_workspace_size bytes): allocating it here would be part of the capture."""
+    if workspace is None:
+        workspace = _steer_workspace(umem, n, n_ports)
+    _check("xsk_gpu_steer_dev", lib().xsk_gpu_steer_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, opts, _ptr(table), n_entries, default_port,
+        n_ports, _ptr(bound), _ptr(actions), _ptr(ports), _ptr(out), _ptr(off), _ptr(workspace), _stream_ptr(stream)))
+
+
+def ingress_steer_dev(umem, descs, n: int, table, n_entries: int, default_port: int, n_ports: int, bound, actions,
+                      ports, out, off, verdicts=None, recs=None, stats=None, workspace=None, stream=None,
+                      opts: int = 0) -> None:
+    """xsk_gpu_ingress_steer_dev: steer_dev(opts) and, on the same stream, echo_dev_indirect(opts) over `out` with the
+    count off[n_ports]; verdicts and records are indexed by position in `out`, so port p's are
+    verdicts[off[p]:off[p + 1]].  Inside a graph capture pass `workspace`, as for steer_dev."""
+    if workspace is None:
+        workspace = _steer_workspace(umem, n, n_ports)
+    _check("xsk_gpu_ingress_steer_dev", lib().xsk_gpu_ingress_steer_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, opts, _ptr(table), n_entries, default_port,
+        n_ports, _ptr(bound), _ptr(actions), _ptr(ports), _ptr(out), _ptr(off), _ptr(verdicts), _ptr(recs),
         _ptr(stats), _ptr(workspace), _stream_ptr(stream)))
 
 
