@@ -587,9 +587,10 @@ int xsk_gpu_steer_dev(const void* d_umem, uint64_t umem_size, const struct xsk_g
  * xsk_gpu_echo_dev_opts() alone leaves over the frames the steering rule redirects; with nothing bound no frame or
  * counter changes; and the opts == 0 caveat (frames of 20 to 33 bytes the reference transform would answer stay as
  * they are behind the reference's filter) holds here too.
- * Not built: xsk_gpu_egress_dev() takes one list that starts at a pointer the host knows, so it serves the whole of
- * d_out (every port's replies on one TX list), not port p's segment, whose start is a device word; a segmented egress
- * is the follow-up.  The host modes are unchanged: there the kernel's XDP program has already chosen the socket. */
+ * Behind it: xsk_gpu_egress_ports_dev() (below) takes d_out, d_verdicts and d_off as they are and builds every port's
+ * own TX and free lists, against that port's own ring room, with nothing in between; xsk_gpu_egress_dev() would serve
+ * the whole of d_out as one list.  The host modes are unchanged: there the kernel's XDP program has already chosen the
+ * socket. */
 int xsk_gpu_ingress_steer_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs, uint32_t n,
                               uint32_t opts, const struct xsk_gpu_steer_entry* d_table, uint32_t n_entries,
                               uint32_t default_port, uint32_t n_ports, const uint64_t* d_bound,
@@ -661,6 +662,81 @@ int xsk_gpu_egress_dev(const struct xsk_gpu_desc* d_descs, const uint8_t* d_verd
                        uint32_t n_max, const uint32_t* d_tx_room, struct xsk_gpu_desc* d_tx, uint64_t* d_free,
                        struct xsk_gpu_egress_counts* d_counts, struct xsk_gpu_stats* d_stats, void* d_workspace,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Egress per steered port (build-added): xsk_gpu_egress_dev()'s rule once per port of the     */
+/* list xsk_gpu_ingress_steer_dev() leaves, so that every port has what the reference keeps    */
+/* per socket in struct xsk_socket_info (src/lib/xsk_utils.h): its own TX ring with its own    */
+/* room, its own free-frame list, its own stats_record.  One call, no word to the host.        */
+/*   d_descs, d_verdicts : n_max descriptors (16-B aligned) and n_max verdict bytes (any       */
+/*                         alignment), e.g. d_out and d_verdicts of the steered ingress        */
+/*   d_off      : n_ports + 1 words in device memory (4-B aligned), n_ports in                 */
+/*                [1, XSK_GPU_STEER_MAX_PORTS]; read when the kernels EXECUTE, like *d_n of    */
+/*                xsk_gpu_egress_dev()                                                         */
+/*   d_tx_room  : n_ports words in device memory (4-B aligned), or NULL; read at execution (a  */
+/*                graph replay may change each port's room).                                   */
+/*                room_p = d_tx_room ? d_tx_room[p] : UINT32_MAX                               */
+/*   d_tx, d_free : room for n_max descriptors (16-B aligned) and n_max uint64_t (8-B aligned) */
+/*   d_counts   : n_ports structs xsk_gpu_egress_counts (4-B aligned)                          */
+/*   d_stats    : the xsk_gpu_stats the transform accumulated into (8-B aligned), or NULL      */
+/*   d_port_stats : n_ports structs xsk_gpu_stats (8-B aligned), or NULL                       */
+/*   d_workspace: xsk_gpu_egress_ports_workspace_size(n_max, n_ports) bytes; may be NULL iff   */
+/*                that is 0 (n_max <= XSK_GPU_LOWLAT_MAX)                                      */
+/* Segments, total for ANY content of d_off:                                                   */
+/*   o_p = min(max(d_off[0], ..., d_off[p]), n_max)   for p = 0 .. n_ports;                    */
+/*   port p's segment is [o_p, o_{p+1}), n_p = o_{p+1} - o_p.  The segments are disjoint and   */
+/*   ascending; for what the steering call writes o_p == d_off[p].  Words that are not         */
+/*   ascending or lie above n_max still give a defined result, and no access leaves            */
+/*   [0, n_max) of any array.  Frames below o_0 or at or above o_{n_ports} are on no list:     */
+/*   their descriptors and verdicts are not read.                                              */
+/* Per port p, the rule of xsk_gpu_egress_dev() over its segment: reply(i) = (d_verdicts[i] == */
+/* XSK_GPU_TX_REPLY); R_p(i) = the replies in [o_p, i), R_p those of the whole segment.        */
+/*   A reply with R_p(i) < room_p is submitted: d_tx[o_p + R_p(i)] = { addr, len, 0 }.         */
+/*   Every other frame of the segment is freed:                                                */
+/*        d_free[o_p + (i - o_p) - min(R_p(i), room_p)] = addr.                                */
+/*   Port p's TX list is d_tx[o_p, o_p + n_tx_p), its free list d_free[o_p, o_p + n_free_p),   */
+/*   both in batch order and both inside the port's own span: neither array needs more than    */
+/*   n_max entries, and no port writes into another's span.                                    */
+/*   d_counts[p] = { n_p, n_tx_p = min(R_p, room_p), n_tx_full_p = R_p - n_tx_p,               */
+/*                   n_free_p = n_p - n_tx_p } for every p; an empty segment gives four zeros. */
+/* Not written: d_tx[o_p + n_tx_p .. o_{p+1}), d_free[o_p + n_free_p .. o_{p+1}), anything     */
+/* outside the segments.                                                                       */
+/* Counters, device-scope 64-bit atomics; a caller that gives neither block pays for neither:  */
+/*   d_stats: tx_packets -= sum_p n_tx_full_p, tx_bytes -= the summed len of the replies not   */
+/*        submitted; no atomic is issued when nothing was left out.                            */
+/*   d_port_stats[p], accumulated, never reset: rx_packets += n_p, rx_bytes += the summed len  */
+/*        of the segment, tx_packets += n_tx_p, tx_bytes += the summed len of the submitted    */
+/*        replies; timestamp untouched.  The per-socket stats_record of the reference.         */
+/* Checked before any device call, -EINVAL: the pointer and alignment rules of                 */
+/* xsk_gpu_egress_dev(); d_off NULL or not 4-B aligned; n_ports outside [1, 64]; d_tx_room not */
+/* 4-B aligned; d_port_stats not 8-B aligned; n_max > XSK_GPU_MAX_BATCH; d_tx == d_descs;      */
+/* d_workspace NULL when xsk_gpu_egress_ports_workspace_size(n_max, n_ports) is nonzero.       */
+/* n_max == 0 zeroes the n_ports counts with an asynchronous memset and launches nothing.      */
+/* Asynchronous on `stream`; allocates nothing, synchronises nothing and reads no device       */
+/* memory from the host, so a stream under graph capture may contain it behind                 */
+/* xsk_gpu_ingress_steer_dev().                                                                */
+/* Identity: with n_ports == 1 and d_off = { 0, k } the call equals xsk_gpu_egress_dev(d_descs,*/
+/* d_verdicts, d_n, n_max, d_tx_room, ...) with *d_n = k -- d_tx, d_free, d_counts[0] and the  */
+/* shared counters -- for k above n_max too.                                                   */
+/* Kernels (xsk_egress_ports.hip): n_max <= XSK_GPU_LOWLAT_MAX is one launch of one workgroup; */
+/* a larger bound is three launches (per-workgroup reply counts; one scan, which also takes    */
+/* the reply prefix at each port boundary and writes d_counts; the scatter) and, only with     */
+/* d_port_stats, a fourth that adds up the scatter's per-workgroup counter sums, a workgroup   */
+/* per port.  Slots come from prefix differences, never from an atomic, so batch order holds   */
+/* within a port.                                                                              */
+/* ------------------------------------------------------------------------------------------ */
+/* Bytes of device workspace xsk_gpu_egress_ports_dev() needs (0 up to XSK_GPU_LOWLAT_MAX): one word and one 32-B
+ * record of counter sums per 256-frame workgroup, one word per port boundary (144 KiB at 2^20 frames).  Word-aligned,
+ * zero or garbage. */
+size_t xsk_gpu_egress_ports_workspace_size(uint32_t n_max, uint32_t n_ports);
+
+int xsk_gpu_egress_ports_dev(const struct xsk_gpu_desc* d_descs, const uint8_t* d_verdicts,
+                             const uint32_t* d_off, uint32_t n_ports, uint32_t n_max,
+                             const uint32_t* d_tx_room,
+                             struct xsk_gpu_desc* d_tx, uint64_t* d_free,
+                             struct xsk_gpu_egress_counts* d_counts,
+                             struct xsk_gpu_stats* d_stats, struct xsk_gpu_stats* d_port_stats,
+                             void* d_workspace, void* stream);
 
 /* The UMEM allocation for the host modes: the reference allocates its UMEM with posix_memalign(getpagesize(),
  * NUM_FRAMES * FRAME_SIZE) (src/lib/xsk_utils.c:132-135); this gives the same kind of memory (anonymous, private,

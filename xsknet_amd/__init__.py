@@ -28,6 +28,7 @@ __all__ = [
     "OPT_STRICT_IPV4", "OPT_VLAN", "OPT_VERIFY_CSUM", "OPT_ALL", "F_IP_CSUM_OK", "F_ICMP_CSUM_OK", "F_VLAN",
     "F_IP_OPTIONS", "OPT_IPV6", "OPT_MASK", "F_IPV6",
     "egress_dev", "egress_workspace_size", "EGRESS_COUNTS_DTYPE",
+    "egress_ports_dev", "egress_ports_workspace_size",
     "STEER_ENTRY_DTYPE", "STEER_PASS", "STEER_MAX_PORTS", "STEER_MAX_ENTRIES", "steer_table_prepare",
     "steer_workspace_size", "steer_dev", "ingress_steer_dev",
 ]
@@ -116,6 +117,8 @@ _SIGS = {
                                  C.c_int),
     "xsk_gpu_egress_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_egress_dev": ([_P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_egress_ports_workspace_size": ([C.c_uint32, C.c_uint32], C.c_size_t),
+    "xsk_gpu_egress_ports_dev": ([_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_steer_table_prepare": ([_P, C.c_uint32], C.c_int),
     "xsk_gpu_steer_workspace_size": ([C.c_uint32, C.c_uint32], C.c_size_t),
     "xsk_gpu_steer_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P,
@@ -368,6 +371,29 @@ def ingress_steer_dev(umem, descs, n: int, table, n_entries: int, default_port: 
         _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), n, opts, _ptr(table), n_entries, default_port,
         n_ports, _ptr(bound), _ptr(actions), _ptr(ports), _ptr(out), _ptr(off), _ptr(verdicts), _ptr(recs),
         _ptr(stats), _ptr(workspace), _stream_ptr(stream)))
+
+
+def egress_ports_workspace_size(n_max: int, n_ports: int) -> int:
+    """xsk_gpu_egress_ports_workspace_size: bytes of device workspace egress_ports_dev needs for a bound of n_max frames
+    and n_ports ports (0 up to LOWLAT_MAX)."""
+    return int(lib().xsk_gpu_egress_ports_workspace_size(n_max, n_ports))
+
+
+def egress_ports_dev(descs, verdicts, off, n_ports: int, n_max: int, tx, free, counts, tx_room=None, stats=None,
+                     port_stats=None, workspace=None, stream=None) -> None:
+    """xsk_gpu_egress_ports_dev: egress_dev's rule once per steered port.  `off` holds n_ports + 1 uint32 words on the
+    device, read when the kernels execute; port p's TX list is tx[off[p]:off[p] + n_tx_p], its free list
+    free[off[p]:off[p] + n_free_p], and counts[p] (n_ports EGRESS_COUNTS_DTYPE) says how long both are.  `tx_room`:
+    n_ports uint32 words on the device (None = unlimited); `stats`: the transform's counter block; `port_stats`:
+    n_ports STATS_DTYPE blocks accumulated per port.  Behind ingress_steer_dev: descs=out, verdicts=verdicts, off=off.
+    Inside a graph capture pass `workspace` (egress_ports_workspace_size bytes) when n_max > LOWLAT_MAX: allocating it
+    here would be part of the capture."""
+    if workspace is None and n_max > LOWLAT_MAX:
+        import torch
+        workspace = torch.empty(egress_ports_workspace_size(n_max, n_ports), dtype=torch.uint8, device=descs.device)
+    _check("xsk_gpu_egress_ports_dev", lib().xsk_gpu_egress_ports_dev(
+        _ptr(descs), _ptr(verdicts), _ptr(off), n_ports, n_max, _ptr(tx_room), _ptr(tx), _ptr(free), _ptr(counts),
+        _ptr(stats), _ptr(port_stats), _ptr(workspace), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,

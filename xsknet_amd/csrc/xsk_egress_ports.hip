@@ -1,0 +1,420 @@
+// xsk_egress_ports.hip — xsk_gpu_egress_ports_dev(): xsk_gpu_egress_dev()'s rule once per steered port.  Behind
+// xsk_gpu_ingress_steer_dev() the redirected descriptors lie grouped by port, port p's at [d_off[p], d_off[p + 1]) with
+// the offsets in device memory; every port gets what the reference keeps per socket (struct xsk_socket_info,
+// src/lib/xsk_utils.h): its own TX list cut at its own ring's room, its own free-frame list, its own stats_record.  Both
+// lists of port p lie inside the port's own span of d_tx / d_free, in batch order (include/xsk_gpu.h).
+//
+// Two paths, the arithmetic of both in xsk_egress_ports.h (host and device):
+//   n_max <= 1024: one launch of one 1024-thread workgroup -- lane per frame, wave ballots, sixteen counts and masks in
+//                  LDS, the prefix at every port boundary from them;
+//   larger:        three launches -- per-workgroup reply counts, one scan (which also takes the prefix at each of the
+//                  n_ports + 1 boundaries, a wave per boundary, and writes d_counts), the in-order scatter -- and, only
+//                  with d_port_stats, a fourth that adds up the scatter's per-workgroup sums, a workgroup per port.
+// Every kernel stages the offsets (a wave's max-scan of the words, then the clamp) and the rooms into LDS in a prologue.
+// A frame's slot is R_p(i) = G(i) - G(o_p) below its port's start: no atomic hands out a slot, no workgroup waits on
+// another.  HBM / latency bound: 17 B in and at most 16 B out per frame, no frame byte touched, no MFMA.
+#include <errno.h>
+
+#include "../../include/xsk_gpu.h"
+#include "xsk_egress_ports.h"
+#include "xsk_hip_util.h"
+
+using namespace xskgpu;
+
+static_assert(kEgSmallMax == XSK_GPU_LOWLAT_MAX, "the one-launch path serves the RX loop's sizes");
+static_assert(kEpMaxPorts == XSK_GPU_STEER_MAX_PORTS, "one offset per steered port and one behind");
+static_assert(kEpMaxPorts == kEgWave, "the prologue scans the offsets in one wave; wave 0 issues the counter atomics");
+static_assert(sizeof(xsk_gpu_egress_counts) == sizeof(EgCounts) && sizeof(EgCounts) == 16, "counts layout");
+static_assert(sizeof(xsk_gpu_desc) == 16, "one 16-B load and store per descriptor");
+
+namespace {
+
+typedef unsigned long long u64;
+
+// What the prologue stages per workgroup: the offsets o_p, the prefixes G(o_p), the rooms.
+struct EpLds {
+    uint32_t o[kEpMaxBounds];
+    uint32_t g[kEpMaxBounds];
+    uint32_t room[kEpMaxPorts];
+};
+
+// Per-port sums of one workgroup, met in LDS before the global atomics.
+struct EpAcc {
+    u64 bytes[kEpMaxPorts], tx_bytes[kEpMaxPorts], unsent_bytes[kEpMaxPorts];
+    uint32_t n[kEpMaxPorts], n_tx[kEpMaxPorts], n_unsent[kEpMaxPorts];
+};
+
+__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kEgWave - 1u); }
+__device__ __forceinline__ uint32_t wave_id() { return threadIdx.x / kEgWave; }
+__device__ __forceinline__ uint32_t below(u64 m, uint32_t lane) { return (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); }
+
+// The prologue (wave 0; the caller's next barrier publishes it): lane l takes word l, an inclusive max-scan over the
+// wave leaves max(d_off[0..l]), the clamp makes it o_l; with 64 ports lane 63 adds the 65th word.  Only
+// d_off[0, n_ports] and d_room[0, n_ports) are read.
+template <bool ROOMS>
+__device__ __forceinline__ void ep_stage(const uint32_t* __restrict__ d_off, uint32_t n_ports, uint32_t n_max,
+                                         const uint32_t* __restrict__ d_room, EpLds* s) {
+    if (wave_id() != 0) return;
+    const uint32_t l = lane_id();
+    uint32_t w = l <= n_ports ? d_off[l] : 0u;
+    for (uint32_t d = 1; d < kEgWave; d <<= 1) {
+        const uint32_t v = __shfl_up(w, d, kEgWave);
+        if (l >= d) w = ep_max(w, v);
+    }
+    if (l <= n_ports) s->o[l] = ep_clamp(w, n_max);
+    if (n_ports == kEpMaxPorts && l == kEgWave - 1u) s->o[kEpMaxPorts] = ep_clamp(ep_max(w, d_off[kEpMaxPorts]), n_max);
+    if (ROOMS && l < n_ports) s->room[l] = eg_room(d_room != nullptr, d_room ? d_room[l] : 0u);
+}
+
+__device__ __forceinline__ void acc_zero(EpAcc* a) {
+    const uint32_t t = threadIdx.x;
+    if (t < kEpMaxPorts) {
+        a->bytes[t] = a->tx_bytes[t] = a->unsent_bytes[t] = 0ull;
+        a->n[t] = a->n_tx[t] = a->n_unsent[t] = 0u;
+    }
+}
+
+// Position i: the descriptor as one 16-B load, the verdict as a byte (any alignment).  Nothing outside [lo, hi) is read.
+__device__ __forceinline__ bool load_frame(const xsk_gpu_desc* __restrict__ descs, const uint8_t* __restrict__ verdicts,
+                                           uint32_t i, uint32_t lo, uint32_t hi, uint4* d) {
+    *d = make_uint4(0u, 0u, 0u, 0u);
+    if (!ep_in(i, lo, hi)) return false;
+    *d = reinterpret_cast<const uint4*>(descs)[i];
+    return verdicts[i] == XSK_GPU_TX_REPLY;
+}
+
+// *d_counts is only 4-B aligned: four word stores.
+__device__ __forceinline__ void store_counts(xsk_gpu_egress_counts* __restrict__ counts, const EgCounts& c) {
+    counts->n = c.n;
+    counts->n_tx = c.n_tx;
+    counts->n_tx_full = c.n_tx_full;
+    counts->n_free = c.n_free;
+}
+
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kEgWave);
+    return v;
+}
+
+// A lane's frame i with g_i = G(i): its owner from the staged offsets, its slot, the store ({ addr, len, 0 } as one 16-B
+// store, or the address as one 8-B store), and -- only when a counter block was given -- the per-port sums.  A port's
+// frames are consecutive lanes, so most waves lie inside one port: such a wave reduces by ballots and shuffles and its
+// lane 0 adds to the port's LDS cells; a wave that holds a boundary adds lane by lane.  After the barrier wave 0, a lane
+// per port, issues the device-scope atomics: four into d_port_stats[p] for a port with frames here, and one pair into
+// d_stats for the whole workgroup, none when no reply of it lies past its port's room.  On the three-stage path
+// (`part` given) the port that owns the workgroup's first position leaves its sums as a record instead, part[wg], for
+// egress_ports_sum_kernel: with few ports nearly every workgroup's set would otherwise meet on one block.
+__device__ __forceinline__ void ep_finish(const uint4& d, bool reply, uint32_t i, uint32_t g_i, const EpLds* s,
+                                          uint32_t n_ports, xsk_gpu_desc* __restrict__ tx,
+                                          uint64_t* __restrict__ free_list, xsk_gpu_stats* stats,
+                                          xsk_gpu_stats* port_stats, EpAcc* acc, EpPart* part, uint32_t wg) {
+    const EpOwner ow = ep_owner(s->o, n_ports, i);
+    bool sub = false, uns = false;
+    if (ow.on) {
+        const uint32_t o_p = s->o[ow.port], g_p = s->g[ow.port], room = s->room[ow.port];
+        const EgSlot sl = ep_slot(reply, i, o_p, g_i, g_p, room);
+        if (sl.tx)
+            reinterpret_cast<uint4*>(tx)[sl.slot] = make_uint4(d.x, d.y, d.z, 0u);  // options = 0, as xsk_gpu__rx_emit()
+        else
+            reinterpret_cast<uint2*>(free_list)[sl.slot] = make_uint2(d.x, d.y);
+        sub = sl.tx;
+        uns = ep_unsent(reply, g_i, g_p, room);
+    }
+    if (!stats && !port_stats) return;  // kernel-uniform
+    const uint32_t key = ow.on ? ow.port : 0xFFFFFFFFu;
+    const uint32_t k0 = __shfl(key, 0, kEgWave);
+    const u64 mu = stats ? __ballot(uns) : 0ull;
+    if (__all(key == k0)) {
+        if (k0 != 0xFFFFFFFFu && (port_stats || mu)) {  // wave-uniform
+            const u64 ms = __ballot(sub);
+            u64 b = 0, bt = 0, bu = 0;
+            if (port_stats) b = wave_sum((u64)d.z);
+            if (port_stats && ms) bt = wave_sum(sub ? (u64)d.z : 0ull);
+            if (mu) bu = wave_sum(uns ? (u64)d.z : 0ull);
+            if (lane_id() == 0) {
+                if (port_stats) {
+                    atomicAdd(&acc->n[k0], kEgWave);
+                    atomicAdd(&acc->bytes[k0], b);
+                    if (ms) {
+                        atomicAdd(&acc->n_tx[k0], (uint32_t)__popcll(ms));
+                        atomicAdd(&acc->tx_bytes[k0], bt);
+                    }
+                }
+                if (mu) {
+                    atomicAdd(&acc->n_unsent[k0], (uint32_t)__popcll(mu));
+                    atomicAdd(&acc->unsent_bytes[k0], bu);
+                }
+            }
+        }
+    } else if (ow.on) {
+        if (port_stats) {
+            atomicAdd(&acc->n[ow.port], 1u);
+            atomicAdd(&acc->bytes[ow.port], (u64)d.z);
+            if (sub) {
+                atomicAdd(&acc->n_tx[ow.port], 1u);
+                atomicAdd(&acc->tx_bytes[ow.port], (u64)d.z);
+            }
+        }
+        if (stats && uns) {
+            atomicAdd(&acc->n_unsent[ow.port], 1u);
+            atomicAdd(&acc->unsent_bytes[ow.port], (u64)d.z);
+        }
+    }
+    __syncthreads();
+    if (wave_id() != 0) return;
+    const uint32_t p = lane_id();
+    uint32_t nu = 0, carry = 0xFFFFFFFFu;
+    u64 bu = 0;
+    if (part && port_stats && ep_wg_carries(wg, s->o[0], s->o[n_ports]))  // wave-uniform
+        carry = ep_owner(s->o, n_ports, wg * kEgFrames).port;
+    if (p < n_ports) {
+        if (port_stats && p == carry) {
+            EpPart* r = part + wg;
+            r->n = acc->n[p];
+            r->n_tx = acc->n_tx[p];
+            r->bytes_lo = (uint32_t)acc->bytes[p];
+            r->bytes_hi = (uint32_t)(acc->bytes[p] >> 32);
+            r->tx_bytes_lo = (uint32_t)acc->tx_bytes[p];
+            r->tx_bytes_hi = (uint32_t)(acc->tx_bytes[p] >> 32);
+        } else if (port_stats && acc->n[p]) {
+            xsk_gpu_stats* ps = port_stats + p;
+            atomicAdd((u64*)&ps->rx_packets, (u64)acc->n[p]);
+            atomicAdd((u64*)&ps->rx_bytes, acc->bytes[p]);
+            if (acc->n_tx[p]) {
+                atomicAdd((u64*)&ps->tx_packets, (u64)acc->n_tx[p]);
+                atomicAdd((u64*)&ps->tx_bytes, acc->tx_bytes[p]);
+            }
+        }
+        if (stats) {
+            nu = acc->n_unsent[p];
+            bu = acc->unsent_bytes[p];
+        }
+    }
+    if (stats) {
+        const u64 c = wave_sum((u64)nu);
+        const u64 t = wave_sum(bu);
+        if (p == 0 && c) {
+            atomicAdd((u64*)&stats->tx_packets, 0ull - c);
+            atomicAdd((u64*)&stats->tx_bytes, 0ull - t);
+        }
+    }
+}
+
+// ---- n_max <= 1024: everything in one workgroup ----
+__global__ __launch_bounds__(kEgSmallThreads) void egress_ports_small_kernel(
+    const xsk_gpu_desc* __restrict__ descs, const uint8_t* __restrict__ verdicts, const uint32_t* __restrict__ d_off,
+    uint32_t n_ports, uint32_t n_max, const uint32_t* __restrict__ d_room, xsk_gpu_desc* __restrict__ tx,
+    uint64_t* __restrict__ free_list, xsk_gpu_egress_counts* __restrict__ counts, xsk_gpu_stats* stats,
+    xsk_gpu_stats* port_stats) {
+    constexpr uint32_t NW = kEgSmallThreads / kEgWave;
+    __shared__ EpLds s;
+    __shared__ EpAcc acc;
+    __shared__ uint32_t s_w[NW];
+    __shared__ uint64_t s_m[NW];
+    const uint32_t t = threadIdx.x;
+    ep_stage<true>(d_off, n_ports, n_max, d_room, &s);
+    acc_zero(&acc);
+    __syncthreads();
+    uint4 d;
+    const bool reply = load_frame(descs, verdicts, t, s.o[0], s.o[n_ports], &d);
+    const u64 m = __ballot(reply);
+    if (lane_id() == 0) {
+        s_w[wave_id()] = (uint32_t)__popcll(m);
+        s_m[wave_id()] = m;
+    }
+    __syncthreads();
+    if (t <= n_ports) s.g[t] = ep_prefix_at(s_w, s_m, NW, s.o[t]);  // G at every boundary (o_p <= 1024: all NW waves)
+    const uint32_t g_i = ep_prefix_at(s_w, s_m, NW, t);
+    __syncthreads();
+    if (t < n_ports) store_counts(counts + t, ep_counts(s.o[t], s.o[t + 1u], s.g[t], s.g[t + 1u], s.room[t]));
+    ep_finish(d, reply, t, g_i, &s, n_ports, tx, free_list, stats, port_stats, &acc, nullptr, 0u);
+}
+
+// ---- larger bounds, stage 1: per-workgroup reply counts over [o_0, o_{n_ports}) (a workgroup outside writes 0) ----
+__global__ __launch_bounds__(kEgFrames) void egress_ports_count_kernel(const uint8_t* __restrict__ verdicts,
+                                                                       const uint32_t* __restrict__ d_off,
+                                                                       uint32_t n_ports, uint32_t n_max,
+                                                                       uint32_t* __restrict__ wg_count) {
+    constexpr uint32_t NW = kEgFrames / kEgWave;
+    __shared__ EpLds s;
+    __shared__ uint32_t s_w[NW];
+    ep_stage<false>(d_off, n_ports, n_max, nullptr, &s);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kEgFrames + threadIdx.x;
+    const bool reply = ep_in(i, s.o[0], s.o[n_ports]) && verdicts[i] == XSK_GPU_TX_REPLY;
+    const u64 m = __ballot(reply);
+    if (lane_id() == 0) s_w[wave_id()] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) wg_count[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// ---- stage 2: exclusive scan of the nwg counts in place (one workgroup of 1024; thread t owns a contiguous run, as
+// xsk_egress.hip's scan), then the prefix at each boundary -- a wave per boundary in turn: the scanned count of the
+// boundary's workgroup plus the replies among the at most 255 verdicts in front of it -- into ws[nwg + p], and
+// d_counts[p] from their differences ----
+__global__ __launch_bounds__(kEgScanThreads) void egress_ports_scan_kernel(
+    uint32_t* ws, uint32_t nwg, const uint8_t* __restrict__ verdicts, const uint32_t* __restrict__ d_off,
+    uint32_t n_ports, uint32_t n_max, const uint32_t* __restrict__ d_room,
+    xsk_gpu_egress_counts* __restrict__ counts) {
+    __shared__ uint32_t sc[kEgScanThreads];
+    __shared__ EpLds s;
+    const uint32_t t = threadIdx.x;
+    ep_stage<true>(d_off, n_ports, n_max, d_room, &s);
+    uint32_t b, e;
+    eg_scan_run(nwg, t, &b, &e);
+    uint32_t sum = 0;
+    for (uint32_t j = b; j < e; ++j) sum += ws[j];
+    sc[t] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < kEgScanThreads; o <<= 1) {  // Hillis-Steele inclusive scan
+        const uint32_t v = t >= o ? sc[t - o] : 0u;
+        __syncthreads();
+        sc[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = sc[t] - sum;  // exclusive prefix of this run
+    for (uint32_t j = b; j < e; ++j) {
+        const uint32_t c = ws[j];
+        ws[j] = run;
+        run += c;
+    }
+    __syncthreads();  // the offsets just written are read below by other waves of this workgroup
+    const uint32_t total = sc[kEgScanThreads - 1u], lo = s.o[0], lane = lane_id();
+    for (uint32_t k = wave_id(); k <= n_ports; k += kEgScanThreads / kEgWave) {  // wave-uniform
+        const uint32_t o = s.o[k], wg = ep_bound_wg(o);
+        uint32_t g = total;
+        if (wg < nwg) {
+            const uint32_t from = ep_bound_from(o, lo);
+            uint32_t c = 0;
+#pragma unroll
+            for (uint32_t q = 0; q < kEgFrames / kEgWave; ++q) {
+                const uint32_t i = wg * kEgFrames + q * kEgWave + lane;
+                const bool r = i >= from && i < o && verdicts[i] == XSK_GPU_TX_REPLY;
+                c += (uint32_t)__popcll(__ballot(r));
+            }
+            g = ws[wg] + c;
+        }
+        if (lane == 0) s.g[k] = g;
+    }
+    __syncthreads();
+    if (t <= n_ports) ws[nwg + t] = s.g[t];
+    if (t < n_ports) store_counts(counts + t, ep_counts(s.o[t], s.o[t + 1u], s.g[t], s.g[t + 1u], s.room[t]));
+}
+
+// ---- stage 3: the in-order scatter of every port's two lists ----
+__global__ __launch_bounds__(kEgFrames) void egress_ports_scatter_kernel(
+    const xsk_gpu_desc* __restrict__ descs, const uint8_t* __restrict__ verdicts, const uint32_t* __restrict__ d_off,
+    uint32_t n_ports, uint32_t n_max, const uint32_t* __restrict__ d_room, const uint32_t* __restrict__ ws, uint32_t nwg,
+    EpPart* __restrict__ part, xsk_gpu_desc* __restrict__ tx, uint64_t* __restrict__ free_list, xsk_gpu_stats* stats,
+    xsk_gpu_stats* port_stats) {
+    constexpr uint32_t NW = kEgFrames / kEgWave;
+    __shared__ EpLds s;
+    __shared__ EpAcc acc;
+    __shared__ uint32_t s_w[NW];
+    const uint32_t t = threadIdx.x;
+    ep_stage<true>(d_off, n_ports, n_max, d_room, &s);
+    if (t <= n_ports) s.g[t] = ws[nwg + t];
+    acc_zero(&acc);
+    __syncthreads();
+    if (!ep_wg_live(blockIdx.x, s.o[0], s.o[n_ports])) return;  // workgroup-uniform
+    const uint32_t i = blockIdx.x * kEgFrames + t;
+    uint4 d;
+    const bool reply = load_frame(descs, verdicts, i, s.o[0], s.o[n_ports], &d);
+    const u64 m = __ballot(reply);
+    if (lane_id() == 0) s_w[wave_id()] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t g_i = ws[blockIdx.x] + below(m, lane_id());
+    for (uint32_t k = 0; k < NW; ++k) g_i += k < wave_id() ? s_w[k] : 0u;
+    ep_finish(d, reply, i, g_i, &s, n_ports, tx, free_list, stats, port_stats, &acc, part, blockIdx.x);
+}
+
+// ---- stage 4, only with d_port_stats: a workgroup per port adds up the records of the scatter workgroups whose first
+// position the port owns and issues the port's one set of atomics ----
+__global__ __launch_bounds__(kEgFrames) void egress_ports_sum_kernel(const uint32_t* __restrict__ d_off, uint32_t n_ports,
+                                                                     uint32_t n_max, const EpPart* __restrict__ part,
+                                                                     xsk_gpu_stats* port_stats) {
+    constexpr uint32_t NW = kEgFrames / kEgWave;
+    __shared__ EpLds s;
+    __shared__ u64 s_r[NW][4];
+    ep_stage<false>(d_off, n_ports, n_max, nullptr, &s);
+    __syncthreads();
+    const uint32_t p = blockIdx.x, b = ep_carry_begin(s.o[p]), e = ep_carry_begin(s.o[p + 1u]);
+    if (b >= e) return;  // workgroup-uniform: no record is this port's
+    u64 n = 0, n_tx = 0, bytes = 0, tx_bytes = 0;
+    for (uint32_t wg = b + threadIdx.x; wg < e; wg += kEgFrames) {
+        const EpPart* r = part + wg;
+        n += r->n;
+        n_tx += r->n_tx;
+        bytes += ep_u64(r->bytes_lo, r->bytes_hi);
+        tx_bytes += ep_u64(r->tx_bytes_lo, r->tx_bytes_hi);
+    }
+    n = wave_sum(n);
+    n_tx = wave_sum(n_tx);
+    bytes = wave_sum(bytes);
+    tx_bytes = wave_sum(tx_bytes);
+    if (lane_id() == 0) {
+        s_r[wave_id()][0] = n;
+        s_r[wave_id()][1] = n_tx;
+        s_r[wave_id()][2] = bytes;
+        s_r[wave_id()][3] = tx_bytes;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4u) {
+        u64 v = 0;
+        for (uint32_t w = 0; w < NW; ++w) v += s_r[w][threadIdx.x];
+        xsk_gpu_stats* ps = port_stats + p;
+        u64* cell = threadIdx.x == 0 ? (u64*)&ps->rx_packets : threadIdx.x == 1 ? (u64*)&ps->tx_packets
+                  : threadIdx.x == 2 ? (u64*)&ps->rx_bytes : (u64*)&ps->tx_bytes;
+        if (v) atomicAdd(cell, v);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t xsk_gpu_egress_ports_workspace_size(uint32_t n_max, uint32_t n_ports) {
+    return ep_workspace_bytes(n_max, n_ports);
+}
+
+int xsk_gpu_egress_ports_dev(const struct xsk_gpu_desc* d_descs, const uint8_t* d_verdicts, const uint32_t* d_off,
+                             uint32_t n_ports, uint32_t n_max, const uint32_t* d_tx_room, struct xsk_gpu_desc* d_tx,
+                             uint64_t* d_free, struct xsk_gpu_egress_counts* d_counts, struct xsk_gpu_stats* d_stats,
+                             struct xsk_gpu_stats* d_port_stats, void* d_workspace, void* stream) {
+    if (!d_descs || !d_tx || !d_free || !d_counts || !d_verdicts || !d_off || ((uintptr_t)d_descs & 15u) ||
+        ((uintptr_t)d_tx & 15u) || ((uintptr_t)d_free & 7u) || ((uintptr_t)d_counts & 3u) || ((uintptr_t)d_off & 3u) ||
+        ((uintptr_t)d_tx_room & 3u) || ((uintptr_t)d_stats & 7u) || ((uintptr_t)d_port_stats & 7u) || n_ports < 1u ||
+        n_ports > kEpMaxPorts || n_max > XSK_GPU_MAX_BATCH || (const void*)d_tx == (const void*)d_descs ||
+        (!d_workspace && n_max > kEgSmallMax))
+        return -EINVAL;
+    const hipStream_t s = (hipStream_t)stream;
+    if (n_max == 0) {
+        HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)n_ports * sizeof(*d_counts), s));
+        return 0;
+    }
+    if (n_max <= kEgSmallMax) {
+        egress_ports_small_kernel<<<dim3(1), dim3(kEgSmallThreads), 0, s>>>(
+            d_descs, d_verdicts, d_off, n_ports, n_max, d_tx_room, d_tx, d_free, d_counts, d_stats, d_port_stats);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    const uint32_t nwg = eg_nwg(n_max);
+    uint32_t* ws = (uint32_t*)d_workspace;
+    EpPart* part = (EpPart*)((char*)d_workspace + ep_part_offset(n_max, n_ports));
+    egress_ports_count_kernel<<<dim3(nwg), dim3(kEgFrames), 0, s>>>(d_verdicts, d_off, n_ports, n_max, ws);
+    HIP_TRY(hipGetLastError());
+    egress_ports_scan_kernel<<<dim3(1), dim3(kEgScanThreads), 0, s>>>(ws, nwg, d_verdicts, d_off, n_ports, n_max,
+                                                                      d_tx_room, d_counts);
+    HIP_TRY(hipGetLastError());
+    egress_ports_scatter_kernel<<<dim3(nwg), dim3(kEgFrames), 0, s>>>(d_descs, d_verdicts, d_off, n_ports, n_max,
+                                                                      d_tx_room, (const uint32_t*)ws, nwg, part, d_tx,
+                                                                      d_free, d_stats, d_port_stats);
+    HIP_TRY(hipGetLastError());
+    if (d_port_stats) {
+        egress_ports_sum_kernel<<<dim3(n_ports), dim3(kEgFrames), 0, s>>>(d_off, n_ports, n_max, part, d_port_stats);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // extern "C"
