@@ -812,6 +812,132 @@ int xsk_gpu_rx_step(xsk_gpu_ctx* ctx, struct xsk_gpu_ring* rx, struct xsk_gpu_ri
  * from the completion ring back to `pool`.  Returns the number moved. */
 uint32_t xsk_gpu_tx_complete(struct xsk_gpu_ring* comp, struct xsk_gpu_frame_pool* pool, uint32_t max);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The RX ring step over rings in device memory (build-added): the device twin of             */
+/* xsk_gpu_rx_step() and xsk_gpu_tx_complete().  The rings' index words, their entry arrays,   */
+/* the frame pool's stack and its count live in device memory; after a call they hold exactly  */
+/* what the host step leaves from the same starting state.  With xsk_gpu_echo_dev_indirect()   */
+/* and xsk_gpu_egress_dev() in the middle, one asynchronous call is a whole RX loop iteration,  */
+/* replayable as a graph with no word to the host.                            */
+/*                                                                                            */
+/* The structs xsk_gpu_ring_dev and xsk_gpu_pool_dev are host memory, read when the call is    */
+/* made; what they point to is device memory, read when the kernels EXECUTE.  The device keeps */
+/* no cached indices: it reads the real words.  Two definitions make the result total for any  */
+/* content of the words:                                                                       */
+/*   used(r) = min((*d_producer - *d_consumer) mod 2^32, size),  free(r) = size - used(r);     */
+/*   pool_n  = min(*d_n_free, capacity).                                                       */
+/* Ring entries are always addressed through the mask (entry i at ring[i & (size - 1)]), pool  */
+/* entries below `capacity`: no content of any word can cause an access outside a ring, the    */
+/* pool, or [0, n_max) of a linear array.                                                      */
+/*                                                                                            */
+/* xsk_gpu_rx_begin_dev(rx, fill, tx, pool, max_batch, d_descs, d_plan, stream): steps 1 and 2 */
+/* of xsk_gpu_rx_step().                                                                       */
+/*   rcvd = min(used(rx), max_batch).                                                          */
+/*   rcvd == 0: only *d_plan is written, with received = 0, refilled = 0 and the other words   */
+/*     as read (tx_room = free(tx)); no ring, pool or d_descs byte changes -- the host step    */
+/*     returns before its refill in this case.                                                 */
+/*   Otherwise: stock = min(free(fill), pool_n);                                               */
+/*     fill entry (fq_prod + i) & mask = d_addr[pool_n - 1 - i] for i < stock (the LIFO pop of */
+/*     the host's refill); *fill.d_producer += stock; *d_n_free = pool_n - stock;              */
+/*     d_descs[i] = RX entry (rx_cons + i) & mask for i < rcvd, all 16 bytes, `options`        */
+/*     included; *d_plan = { rcvd, free(tx), stock, rx_cons, fq_prod, pool_n, 0, 0 }.          */
+/*   The RX consumer word is not advanced here.  d_descs: max_batch descriptors (16-B          */
+/*   aligned); d_plan: one struct xsk_gpu_rx_plan (4-B aligned).  stock is bounded by the fill */
+/*   ring and the pool, not by max_batch.                                                      */
+/*                                                                                            */
+/* xsk_gpu_rx_end_dev(rx, tx, pool, d_plan, d_tx, d_free, d_counts, n_max, d_res, stream): the  */
+/* ring half of step 4 and step 5, behind xsk_gpu_egress_dev().  With c = *d_counts:           */
+/*   n_tx = min(c.n_tx, n_max, free(tx)): TX entry (*tx.d_producer + k) & mask = d_tx[k] for   */
+/*     k < n_tx, all 16 bytes; *tx.d_producer += n_tx.                                         */
+/*   pushed = min(min(c.n_free, n_max), capacity - pool_n): d_addr[pool_n + j] = d_free[j] for */
+/*     j < pushed (the host's pool_push() in batch order; what does not fit is dropped, as on  */
+/*     the host); *d_n_free = pool_n + pushed.  pool_n is read at execution: after begin's pop.*/
+/*   *rx.d_consumer += min(d_plan->received, n_max).                                           */
+/*   *d_res = { that release count, n_tx, c.n_tx_full, d_plan->refilled }: a struct            */
+/*     xsk_gpu_rx_result in device memory (4-B aligned), written, not accumulated; may be NULL.*/
+/*                                                                                            */
+/* xsk_gpu_rx_step_dev(d_umem, umem_size, rx, fill, tx, pool, max_batch, opts, d_stats, d_res,  */
+/* d_workspace, stream): pure composition on one stream, in this order: begin;                 */
+/* xsk_gpu_echo_dev_indirect(d_descs, &plan->received, max_batch, opts, d_verdicts, NULL,      */
+/* d_stats); xsk_gpu_egress_dev(d_descs, d_verdicts, &plan->received, max_batch,               */
+/* &plan->tx_room, d_tx, d_free, d_counts, d_stats, ...); end.  Every intermediate array is    */
+/* carved from d_workspace: xsk_gpu_rx_step_dev_workspace_size(max_batch) bytes of device      */
+/* memory, 16-B aligned, zero or garbage.  d_stats (device memory, 8-B aligned, or NULL) ends  */
+/* where the host step's `stats` ends: the transform counts rx and every reply, the egress     */
+/* takes back the replies that found the ring full.  The host step's bound of                  */
+/* XSK_GPU_RX_MAX_STEP frames does not apply: max_batch may be anything up to                  */
+/* XSK_GPU_MAX_BATCH.                                                                          */
+/*                                                                                            */
+/* xsk_gpu_tx_complete_dev(comp, pool, max, d_moved, stream): n = min(used(comp), max); the    */
+/* first min(n, capacity - pool_n) entries are pushed onto the pool in ring order; the         */
+/* consumer word advances by n; *d_moved = n (4-B aligned device word, may be NULL).  max == 0 */
+/* launches nothing and sets *d_moved to 0 with an asynchronous memset when given.             */
+/*                                                                                            */
+/* Checked before any device call, -EINVAL: a NULL struct or member pointer; a nonzero         */
+/* `reserved`; index words and d_n_free not 4-B aligned; a descriptor ring, d_descs or d_tx    */
+/* not 16-B aligned; an address ring, d_addr or d_free not 8-B aligned; d_plan, d_counts,      */
+/* d_res, d_moved not 4-B aligned (d_plan, d_counts NULL); size not a power of two in          */
+/* [1, 2^31]; capacity == 0; max_batch / n_max outside [1, XSK_GPU_MAX_BATCH] (max above it);  */
+/* for the step also the rules of the two composed calls: d_umem NULL or not 16-B aligned,     */
+/* umem_size not a multiple of 16 or >= 2^48, option bits outside XSK_GPU_OPT_MASK, d_stats    */
+/* not 8-B aligned, d_workspace NULL or not 16-B aligned.                                      */
+/* The calls are asynchronous on `stream`, allocate nothing, synchronise nothing and read no   */
+/* device memory from the host, so a stream under graph capture may contain them.              */
+/*                                                                                            */
+/* Ring protocol order: entries are stored before the index word that covers them, and no      */
+/* launch stores an index word for entries that a later launch stores.  The calls are ordered  */
+/* against a peer by the stream alone: a producer or consumer running CONCURRENTLY on another  */
+/* stream or agent, and rings in mapped host memory, are out of scope -- nothing here promises */
+/* that an entry is visible to another agent while a launch is still running.                  */
+/* Kernels (xsk_ring_dev.hip): a bound <= XSK_GPU_LOWLAT_MAX is one launch of one workgroup    */
+/* for begin, for end and for tx_complete; a larger bound splits each at kernel boundaries     */
+/* (begin: plan, copy grid, publish; end and tx_complete: copy grid, publish).                 */
+/* ------------------------------------------------------------------------------------------ */
+struct xsk_gpu_ring_dev {      /* 32 bytes; the struct is host memory, what it points to is device memory */
+    uint32_t* d_producer;      /* free-running index word, 4-B aligned */
+    uint32_t* d_consumer;      /* free-running index word, 4-B aligned */
+    void*     d_ring;          /* `size` entries: struct xsk_gpu_desc (16-B aligned) for RX/TX,
+                                  uint64_t (8-B aligned) for fill/completion; entry i at ring[i & (size-1)] */
+    uint32_t  size;            /* power of two, 1 .. 2^31 */
+    uint32_t  reserved;        /* 0 */
+};
+struct xsk_gpu_pool_dev {      /* 24 bytes: struct xsk_gpu_frame_pool with stack and count in device memory */
+    uint64_t* d_addr;          /* `capacity` entries, 8-B aligned */
+    uint32_t* d_n_free;        /* 4-B aligned */
+    uint32_t  capacity;
+    uint32_t  reserved;        /* 0 */
+};
+struct xsk_gpu_rx_plan {       /* 32 bytes, device memory, 4-B aligned: what begin decided, read by what follows */
+    uint32_t received;         /* usable as d_n of xsk_gpu_echo_dev_indirect / xsk_gpu_egress_dev */
+    uint32_t tx_room;          /* usable as d_tx_room of xsk_gpu_egress_dev */
+    uint32_t refilled;
+    uint32_t rx_cons, fq_prod, pool_n;   /* the index words and pool count as read (snapshot) */
+    uint32_t reserved[2];
+};
+
+/* Bytes of device workspace xsk_gpu_rx_step_dev() needs for a bound of max_batch frames: the plan, the egress counts,
+ * max_batch descriptors, TX entries, free addresses and verdicts, and xsk_gpu_egress_workspace_size(max_batch)
+ * (48 + 41 B per frame, rounded up to 16). */
+size_t xsk_gpu_rx_step_dev_workspace_size(uint32_t max_batch);
+
+int xsk_gpu_rx_begin_dev(const struct xsk_gpu_ring_dev* rx, const struct xsk_gpu_ring_dev* fill,
+                         const struct xsk_gpu_ring_dev* tx, const struct xsk_gpu_pool_dev* pool, uint32_t max_batch,
+                         struct xsk_gpu_desc* d_descs, struct xsk_gpu_rx_plan* d_plan, void* stream);
+
+int xsk_gpu_rx_end_dev(const struct xsk_gpu_ring_dev* rx, const struct xsk_gpu_ring_dev* tx,
+                       const struct xsk_gpu_pool_dev* pool, const struct xsk_gpu_rx_plan* d_plan,
+                       const struct xsk_gpu_desc* d_tx, const uint64_t* d_free,
+                       const struct xsk_gpu_egress_counts* d_counts, uint32_t n_max, struct xsk_gpu_rx_result* d_res,
+                       void* stream);
+
+int xsk_gpu_rx_step_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_ring_dev* rx,
+                        const struct xsk_gpu_ring_dev* fill, const struct xsk_gpu_ring_dev* tx,
+                        const struct xsk_gpu_pool_dev* pool, uint32_t max_batch, uint32_t opts,
+                        struct xsk_gpu_stats* d_stats, struct xsk_gpu_rx_result* d_res, void* d_workspace, void* stream);
+
+int xsk_gpu_tx_complete_dev(const struct xsk_gpu_ring_dev* comp, const struct xsk_gpu_pool_dev* pool, uint32_t max,
+                            uint32_t* d_moved, void* stream);
+
 /* Pipelined RX loop: xsk_gpu_rx_step with up to `depth` batches in flight, so that one queue's steps overlap their
  * PCIe round trips instead of paying one per step.  The object owns up to `depth` contexts of `mode` over one
  * registration of the UMEM and hands batches to them in turn.  A LOWLAT pipe stops adding contexts at the first one

@@ -31,6 +31,8 @@ __all__ = [
     "egress_ports_dev", "egress_ports_workspace_size",
     "STEER_ENTRY_DTYPE", "STEER_PASS", "STEER_MAX_PORTS", "STEER_MAX_ENTRIES", "steer_table_prepare",
     "steer_workspace_size", "steer_dev", "ingress_steer_dev",
+    "RingDev", "PoolDev", "RxPlan", "rx_begin_dev", "rx_end_dev", "rx_step_dev", "rx_step_dev_workspace_size",
+    "tx_complete_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -102,6 +104,36 @@ class RxResult(C.Structure):
 
 assert C.sizeof(Ring) == 48 and C.sizeof(FramePool) == 16 and C.sizeof(RxResult) == 16
 
+
+class RingDev(C.Structure):
+    """struct xsk_gpu_ring_dev: a ring whose index words and entries live in device memory (the struct itself is host
+    memory, read when a call is made)."""
+    _fields_ = [("d_producer", C.c_void_p), ("d_consumer", C.c_void_p), ("d_ring", C.c_void_p), ("size", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    @classmethod
+    def of(cls, producer, consumer, ring, size: int) -> "RingDev":
+        """From torch device tensors: two uint32 words (int32 tensors of one element) and the entry array."""
+        return cls(_ptr(producer), _ptr(consumer), _ptr(ring), size, 0)
+
+
+class PoolDev(C.Structure):
+    """struct xsk_gpu_pool_dev: struct xsk_gpu_frame_pool with the stack and its count in device memory."""
+    _fields_ = [("d_addr", C.c_void_p), ("d_n_free", C.c_void_p), ("capacity", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def of(cls, addr, n_free, capacity: int) -> "PoolDev":
+        return cls(_ptr(addr), _ptr(n_free), capacity, 0)
+
+
+class RxPlan(C.Structure):
+    """struct xsk_gpu_rx_plan (device memory): what rx_begin_dev decided."""
+    _fields_ = [("received", C.c_uint32), ("tx_room", C.c_uint32), ("refilled", C.c_uint32), ("rx_cons", C.c_uint32),
+                ("fq_prod", C.c_uint32), ("pool_n", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(RingDev) == 32 and C.sizeof(PoolDev) == 24 and C.sizeof(RxPlan) == 32
+
 _lib: Optional[C.CDLL] = None
 
 _P = C.c_void_p
@@ -139,6 +171,14 @@ _SIGS = {
     "xsk_gpu_rx_step": ([_P, C.POINTER(Ring), C.POINTER(Ring), C.POINTER(Ring), C.POINTER(FramePool), C.c_uint32,
                          _P, C.POINTER(RxResult)], C.c_int),
     "xsk_gpu_tx_complete": ([C.POINTER(Ring), C.POINTER(FramePool), C.c_uint32], C.c_uint32),
+    "xsk_gpu_rx_step_dev_workspace_size": ([C.c_uint32], C.c_size_t),
+    "xsk_gpu_rx_begin_dev": ([C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32,
+                              _P, _P, _P], C.c_int),
+    "xsk_gpu_rx_end_dev": ([C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(PoolDev), _P, _P, _P, _P, C.c_uint32, _P,
+                            _P], C.c_int),
+    "xsk_gpu_rx_step_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
+                             C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_tx_complete_dev": ([C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -394,6 +434,49 @@ def egress_ports_dev(descs, verdicts, off, n_ports: int, n_max: int, tx, free, c
     _check("xsk_gpu_egress_ports_dev", lib().xsk_gpu_egress_ports_dev(
         _ptr(descs), _ptr(verdicts), _ptr(off), n_ports, n_max, _ptr(tx_room), _ptr(tx), _ptr(free), _ptr(counts),
         _ptr(stats), _ptr(port_stats), _ptr(workspace), _stream_ptr(stream)))
+
+
+def rx_step_dev_workspace_size(max_batch: int) -> int:
+    """xsk_gpu_rx_step_dev_workspace_size: bytes of device workspace rx_step_dev needs for a bound of max_batch frames."""
+    return int(lib().xsk_gpu_rx_step_dev_workspace_size(max_batch))
+
+
+def rx_begin_dev(rx: RingDev, fill: RingDev, tx: RingDev, pool: PoolDev, max_batch: int, descs, plan,
+                 stream=None) -> None:
+    """xsk_gpu_rx_begin_dev: peek up to max_batch RX entries into `descs` (max_batch descriptors), refill the fill ring
+    from the pool and leave what was decided in `plan` (one RxPlan, 32 bytes), all on the device: steps 1 and 2 of
+    xsk_gpu_rx_step over rings in device memory.  plan[0:4] serves as `count` and plan[4:8] as `tx_room` of
+    echo_dev_indirect / egress_dev."""
+    _check("xsk_gpu_rx_begin_dev", lib().xsk_gpu_rx_begin_dev(
+        C.byref(rx), C.byref(fill), C.byref(tx), C.byref(pool), max_batch, _ptr(descs), _ptr(plan),
+        _stream_ptr(stream)))
+
+
+def rx_end_dev(rx: RingDev, tx: RingDev, pool: PoolDev, plan, tx_list, free, counts, n_max: int, res=None,
+               stream=None) -> None:
+    """xsk_gpu_rx_end_dev: egress_dev's TX list onto the TX ring, its free list onto the pool, the RX entries released,
+    `res` (one RxResult in device memory, 16 bytes, or None) written: step 5 and the ring half of step 4."""
+    _check("xsk_gpu_rx_end_dev", lib().xsk_gpu_rx_end_dev(
+        C.byref(rx), C.byref(tx), C.byref(pool), _ptr(plan), _ptr(tx_list), _ptr(free), _ptr(counts), n_max, _ptr(res),
+        _stream_ptr(stream)))
+
+
+def rx_step_dev(umem, rx: RingDev, fill: RingDev, tx: RingDev, pool: PoolDev, max_batch: int, workspace, stats=None,
+                res=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_rx_step_dev: one RX loop iteration over rings, pool and UMEM in device memory -- rx_begin_dev,
+    echo_dev_indirect, egress_dev, rx_end_dev on one stream, the intermediate arrays carved from `workspace`
+    (rx_step_dev_workspace_size(max_batch) bytes, 16-B aligned).  `stats`: one STATS_DTYPE on the device, accumulated;
+    `res`: one RxResult on the device, written."""
+    _check("xsk_gpu_rx_step_dev", lib().xsk_gpu_rx_step_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), C.byref(tx), C.byref(pool),
+        max_batch, opts, _ptr(stats), _ptr(res), _ptr(workspace), _stream_ptr(stream)))
+
+
+def tx_complete_dev(comp: RingDev, pool: PoolDev, max_entries: int, moved=None, stream=None) -> None:
+    """xsk_gpu_tx_complete_dev: up to max_entries completed TX frames from the completion ring back onto the pool;
+    `moved` (a uint32 word on the device, or None) receives the count."""
+    _check("xsk_gpu_tx_complete_dev", lib().xsk_gpu_tx_complete_dev(
+        C.byref(comp), C.byref(pool), max_entries, _ptr(moved), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,
