@@ -25,17 +25,9 @@
 
 #include "../../include/xsk_gpu.h"
 #include "../../xsknet_amd/csrc/xsk_egress_ports.h"
+#include "compact_replay.h"  // CHECK, and the scan stage replayed
 
 using namespace xskgpu;
-
-#define CHECK(c, ...)                     \
-    do {                                  \
-        if (!(c)) {                       \
-            fprintf(stderr, __VA_ARGS__); \
-            fprintf(stderr, "\n");        \
-            exit(1);                      \
-        }                                 \
-    } while (0)
 
 static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd64() {  // xorshift64*
@@ -288,7 +280,7 @@ static void device_paths(const Case& k, const Ref& ref, Got* r) {
         CHECK(r->port_sets <= k.n_ports, "%s: more per-port sets than ports", k.what);
         return;
     }
-    const uint32_t nwg = eg_nwg(k.n_max);
+    const uint32_t nwg = cp_nwg(k.n_max);
     CHECK(ep_part_offset(k.n_max, k.n_ports) == ((size_t)nwg + k.n_ports + 1) * 4 && sizeof(EpPart) == 32 &&
               ep_workspace_bytes(k.n_max, k.n_ports) == ep_part_offset(k.n_max, k.n_ports) + (size_t)nwg * 32,
           "workspace");
@@ -306,29 +298,7 @@ static void device_paths(const Case& k, const Ref& ref, Got* r) {
         ws[wg] = c;
     }
     // stage 2: the scan over runs, then a prefix per boundary
-    static uint32_t sc[kEgScanThreads], sum[kEgScanThreads];
-    uint32_t next = 0;
-    for (uint32_t t = 0; t < kEgScanThreads; ++t) {
-        uint32_t b, e;
-        eg_scan_run(nwg, t, &b, &e);
-        CHECK(b == next && b <= e && e <= nwg, "scan runs");
-        next = e;
-        sum[t] = 0;
-        for (uint32_t j = b; j < e; ++j) sum[t] += ws[j];
-    }
-    CHECK(next == nwg, "scan runs do not cover the counts");
-    uint32_t acc = 0;
-    for (uint32_t t = 0; t < kEgScanThreads; ++t) sc[t] = (acc += sum[t]);  // (what the Hillis-Steele rounds leave)
-    for (uint32_t t = 0; t < kEgScanThreads; ++t) {
-        uint32_t b, e, run = sc[t] - sum[t];
-        eg_scan_run(nwg, t, &b, &e);
-        for (uint32_t j = b; j < e; ++j) {
-            const uint32_t c = ws[j];
-            ws[j] = run;
-            run += c;
-        }
-    }
-    const uint32_t total = sc[kEgScanThreads - 1];
+    const uint32_t total = replay_scan_cells(ws, nwg, replay_put_before);
     for (uint32_t b = 0; b <= k.n_ports; ++b) {
         const uint32_t o = s.o[b], wg = ep_bound_wg(o);
         uint32_t g = total;
@@ -620,7 +590,7 @@ int main(void) {
             }
     }
     // the largest bound the call accepts: the sizes stay inside 32 bits
-    const uint32_t big = XSK_GPU_MAX_BATCH, nwg = eg_nwg(big);
+    const uint32_t big = XSK_GPU_MAX_BATCH, nwg = cp_nwg(big);
     CHECK(ep_workspace_bytes(big, 64) == ((size_t)nwg + 65) * 4 + (size_t)nwg * 32 && (uint64_t)nwg * kEgFrames <= 0x100000000ull,
           "largest bound");
     CHECK(ep_carry_begin(big) == nwg && ep_carry_begin(0) == 0 && ep_carry_begin(1) == 1 && ep_carry_begin(256) == 1 &&

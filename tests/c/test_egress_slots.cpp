@@ -18,17 +18,9 @@
 
 #include "../../include/xsk_gpu.h"
 #include "../../xsknet_amd/csrc/xsk_egress.h"
+#include "compact_replay.h"  // CHECK, and the scan stage replayed
 
 using namespace xskgpu;
-
-#define CHECK(c, ...)                     \
-    do {                                  \
-        if (!(c)) {                       \
-            fprintf(stderr, __VA_ARGS__); \
-            fprintf(stderr, "\n");        \
-            exit(1);                      \
-        }                                 \
-    } while (0)
 
 static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd64() {  // xorshift64*
@@ -150,7 +142,7 @@ static void device_paths(const xsk_gpu_desc* descs, const uint8_t* verdict, bool
         r->c = eg_counts(n, total, room);
         return;
     }
-    const uint32_t nwg = eg_nwg(n_max);
+    const uint32_t nwg = cp_nwg(n_max);
     CHECK((uint64_t)nwg * kEgFrames >= n_max && (uint64_t)(nwg - 1) * kEgFrames < n_max, "nwg");
     CHECK(eg_workspace_bytes(n_max) == (size_t)nwg * 4, "workspace");
     uint32_t* ws = (uint32_t*)malloc(eg_workspace_bytes(n_max));
@@ -165,34 +157,13 @@ static void device_paths(const xsk_gpu_desc* descs, const uint8_t* verdict, bool
     }
     CHECK(covered == n, "the workgroups' frames do not add up to n");
     // stage 2: thread t owns a run; the runs partition [0, nwg)
-    static uint32_t s[kEgScanThreads], sum[kEgScanThreads];
-    uint32_t next = 0;
-    for (uint32_t t = 0; t < kEgScanThreads; ++t) {
-        uint32_t b, e;
-        eg_scan_run(nwg, t, &b, &e);
-        CHECK(b == next && b <= e && e <= nwg, "scan runs");
-        next = e;
-        sum[t] = 0;
-        for (uint32_t j = b; j < e; ++j) sum[t] += ws[j];
-    }
-    CHECK(next == nwg, "scan runs do not cover the counts");
-    uint32_t acc = 0;
-    for (uint32_t t = 0; t < kEgScanThreads; ++t) s[t] = (acc += sum[t]);  // (what the Hillis-Steele rounds leave)
-    for (uint32_t t = 0; t < kEgScanThreads; ++t) {
-        uint32_t b, e, run = s[t] - sum[t];
-        eg_scan_run(nwg, t, &b, &e);
-        for (uint32_t j = b; j < e; ++j) {
-            const uint32_t c = ws[j];
-            ws[j] = run;
-            run += c;
-        }
-    }
-    r->c = eg_counts(n, s[kEgScanThreads - 1], room);
+    const uint32_t r_total = replay_scan_cells(ws, nwg, replay_put_before);
+    r->c = eg_counts(n, r_total, room);
     for (uint32_t wg = 0; wg < nwg; ++wg) {  // stage 3
         if (eg_wg_frames(n, wg) == 0) continue;
         uint32_t total = 0;
         scatter_wg(descs, verdict, n, room, wg * kEgFrames, kEgFrames, ws[wg], r, &total);
-        CHECK(total == (wg + 1 < nwg ? ws[wg + 1] : s[kEgScanThreads - 1]), "offsets are not the running reply count");
+        CHECK(total == (wg + 1 < nwg ? ws[wg + 1] : r_total), "offsets are not the running reply count");
     }
     free(ws);
 }
@@ -269,7 +240,7 @@ static void one_case(uint32_t n_max, bool have_n, uint32_t word_n, int pattern, 
     CHECK(got.lost_packets == ref.lost_packets && got.lost_bytes == ref.lost_bytes && got.lost_packets == got.c.n_tx_full,
           "counters: n_max %u n %u pattern %d room %u", n_max, n, pattern, room);
     CHECK(got.c.n_tx_full || !got.atomic_pairs, "atomics issued with n_tx_full == 0");
-    CHECK(got.atomic_pairs <= (n_max <= kEgSmallMax ? 1u : eg_nwg(n_max)), "more than one pair per workgroup");
+    CHECK(got.atomic_pairs <= (n_max <= kEgSmallMax ? 1u : cp_nwg(n_max)), "more than one pair per workgroup");
     free(descs);
     free(verdict);
     free(ref.tx);
@@ -277,6 +248,28 @@ static void one_case(uint32_t n_max, bool have_n, uint32_t word_n, int pattern, 
     free(got.tx);
     free(got.fr);
     ++g_cases;
+}
+
+// cp_scan_run against the expression the filter's scan used before it took cp_scan_run -- b = t * per, e = min(b + per,
+// nwg) in 32 bits, the run taken when b < e -- at every thread: the same cells, and a partition of [0, nwg).  0xFFFFFF is
+// cp_nwg(XSK_GPU_MAX_BATCH); with per <= 16384 nothing in the 32-bit form wraps.
+static void scan_runs_agree() {
+    const uint32_t nwgs[] = {0, 1, 2, 1023, 1024, 1025, 2047, 2048, 2049, 65536, 0xFFFFFF};
+    static_assert(XSK_GPU_MAX_BATCH / kCpFrames == 0xFFFFFF && XSK_GPU_MAX_BATCH % kCpFrames == 0, "the largest grid");
+    for (uint32_t nwg : nwgs) {
+        const uint32_t per = (nwg + 1023u) / 1024u;
+        uint32_t next = 0;
+        for (uint32_t t = 0; t < kCpScanThreads; ++t) {
+            uint32_t b, e;
+            cp_scan_run(nwg, t, &b, &e);
+            CHECK(b == next && b <= e && e <= nwg, "scan runs: nwg %u thread %u", nwg, t);
+            next = e;
+            const uint32_t ob = t * per, oe = ob + per < nwg ? ob + per : nwg;
+            CHECK(ob < oe ? b == ob && e == oe : b == e, "nwg %u thread %u: [%u, %u), formerly [%u, %u) if not empty", nwg,
+                  t, b, e, ob, oe);
+        }
+        CHECK(next == nwg && per <= 16384u, "scan runs do not cover [0, %u)", nwg);
+    }
 }
 
 int main(void) {
@@ -304,12 +297,13 @@ int main(void) {
         }
     }
     // the largest bound the call accepts: the sizes stay inside 32 bits, the scan's runs inside the counts
-    const uint32_t big = XSK_GPU_MAX_BATCH, nwg = eg_nwg(big);
+    const uint32_t big = XSK_GPU_MAX_BATCH, nwg = cp_nwg(big);
     CHECK((uint64_t)nwg * kEgFrames >= big && eg_workspace_bytes(big) == (size_t)nwg * 4, "largest bound");
     uint32_t b, e;
-    eg_scan_run(nwg, kEgScanThreads - 1, &b, &e);
+    cp_scan_run(nwg, kEgScanThreads - 1, &b, &e);
     CHECK(e == nwg && b <= e, "largest bound: the last run");
     CHECK(eg_wg_frames(big, nwg - 1) == big - (nwg - 1) * kEgFrames && eg_wg_frames(big, nwg) == 0, "largest bound");
+    scan_runs_agree();
     printf("egress slots ok (%llu cases)\n", (unsigned long long)g_cases);
     return 0;
 }

@@ -24,17 +24,9 @@
 
 #include "../../include/xsk_gpu.h"
 #include "../../xsknet_amd/csrc/xsk_steer.h"
+#include "compact_replay.h"  // CHECK, and the scan stage replayed
 
 using namespace xskgpu;
-
-#define CHECK(c, ...)                     \
-    do {                                  \
-        if (!(c)) {                       \
-            fprintf(stderr, __VA_ARGS__); \
-            fprintf(stderr, "\n");        \
-            exit(1);                      \
-        }                                 \
-    } while (0)
 
 static uint64_t g_rng = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd64() {  // xorshift64*
@@ -257,7 +249,7 @@ static void partition_case(uint32_t n, uint32_t n_ports, int pattern) {
         descs[i] = xsk_gpu_desc{0x1000ull * i + 7, 60 + i % 1000, i};
         total += red[i];
     }
-    const uint32_t nwg = st_nwg(n), cells = st_cells(n_ports, nwg);
+    const uint32_t nwg = cp_nwg(n), cells = st_cells(n_ports, nwg);
     CHECK(st_workspace_bytes(n, n_ports) == (size_t)cells * 4, "workspace");
     uint32_t* count = exact<uint32_t>(cells);
     uint32_t* off = exact<uint32_t>(n_ports + 1);
@@ -281,19 +273,7 @@ static void partition_case(uint32_t n, uint32_t n_ports, int pattern) {
         uint32_t* row = count + st_cell(p, 0, nwg);
         uint32_t row_total = 0;
         for (uint32_t j = 0; j < nwg; ++j) row_total += row[j];
-        uint32_t run = 0, written = 0;
-        for (uint32_t t = 0; t < kStScanThreads; ++t) {
-            uint32_t b, e;
-            st_scan_run(nwg, t, &b, &e);
-            CHECK(b <= e && e <= nwg && b == written, "scan runs");
-            for (uint32_t j = b; j < e; ++j) {
-                const uint32_t c = row[j];
-                row[j] = st_scanned_cell(j, run, row_total);
-                run += c;
-            }
-            written = e;
-        }
-        CHECK(written == nwg && run == row_total, "the runs cover the row");
+        CHECK(replay_scan_cells(row, nwg, st_scanned_cell) == row_total, "the row's total");
     }
     // stage 3's prologue: the totals -> the ports' first slots
     std::vector<uint32_t> base(n_ports);
@@ -339,7 +319,7 @@ static void test_partition() {
         for (uint32_t np : ports)
             for (int pattern = 0; pattern < 5; ++pattern) partition_case(n, np, pattern);
     // 1025 workgroups: the first batch at which a thread of a row's scan owns two cells
-    CHECK(st_scan_per(st_nwg(262145)) == 2 && st_scan_per(st_nwg(262144)) == 1, "262145 frames");
+    CHECK(cp_scan_per(cp_nwg(262145)) == 2 && cp_scan_per(cp_nwg(262144)) == 1, "262145 frames");
     for (uint32_t np : {3u, 64u})
         for (int pattern = 0; pattern < 2; ++pattern) partition_case(262145, np, pattern);
     for (int k = 0; k < 200; ++k) partition_case(1 + rnd(3000), 1 + rnd(63), 0);

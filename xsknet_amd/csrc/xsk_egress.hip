@@ -8,8 +8,8 @@
 //
 // Two paths, the arithmetic of both in xsk_egress.h (host and device):
 //   n_max <= 1024: one launch of one 1024-thread workgroup — lane per frame, wave ballots, sixteen counts in LDS;
-//   larger:        the filter's three launches (xsk_classify.hip) — per-workgroup reply counts, one exclusive scan
-//                  (which also writes the counts), the in-order scatter of both lists.
+//   larger:        the three launches of the compaction core (xsk_compact.h) — per-workgroup reply counts, one
+//                  exclusive scan (which also writes the counts), the in-order scatter of both lists.
 // Every kernel reads the count and the room in a prologue of scalar loads.  HBM / latency bound: 17 B in and at most
 // 16 B out per frame, no frame byte touched, no MFMA.
 #include <errno.h>
@@ -40,61 +40,26 @@ __device__ __forceinline__ EgIn eg_prologue(const uint32_t* __restrict__ d_n, ui
     return in;
 }
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kEgWave - 1u); }
-__device__ __forceinline__ uint32_t wave_id() { return threadIdx.x / kEgWave; }
-__device__ __forceinline__ uint32_t below(u64 m, uint32_t lane) { return (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); }
-
-// Frame i of the batch: the descriptor as one 16-B load, the verdict as a byte (any alignment; consecutive lanes read
-// consecutive bytes).  Nothing at an index >= n is read.
-__device__ __forceinline__ bool load_frame(const xsk_gpu_desc* __restrict__ descs, const uint8_t* __restrict__ verdicts,
-                                           uint32_t i, uint32_t n, uint4* d) {
-    *d = make_uint4(0u, 0u, 0u, 0u);
-    if (i >= n) return false;
-    *d = reinterpret_cast<const uint4*>(descs)[i];
-    return verdicts[i] == XSK_GPU_TX_REPLY;
-}
-
-// Frame i < n to its list: { addr, len, 0 } as one 16-B store, or the address as one 8-B store.
-__device__ __forceinline__ void store_frame(const uint4& d, bool reply, uint32_t i, uint32_t r_below, uint32_t room,
-                                            xsk_gpu_desc* __restrict__ tx, uint64_t* __restrict__ free_list) {
-    const EgSlot s = eg_slot(reply, i, r_below, room);
-    if (s.tx)
-        reinterpret_cast<uint4*>(tx)[s.slot] = make_uint4(d.x, d.y, d.z, 0u);  // options = 0, as xsk_gpu__rx_emit()
-    else
-        reinterpret_cast<uint2*>(free_list)[s.slot] = make_uint2(d.x, d.y);
-}
-
-// *d_counts is only 4-B aligned: four word stores.
-__device__ __forceinline__ void store_counts(xsk_gpu_egress_counts* __restrict__ counts, const EgCounts& c) {
-    counts->n = c.n;
-    counts->n_tx = c.n_tx;
-    counts->n_tx_full = c.n_tx_full;
-    counts->n_free = c.n_free;
-}
-
 // tx_packets / tx_bytes taken back for the workgroup's replies past the room: each wave reduces its own, wave 0 the
 // NW partials, lane 0 issues the one pair of device-scope atomics -- none when the workgroup has no such reply.
 template <uint32_t NW>
 __device__ __forceinline__ void take_back(bool unsent, uint32_t len, uint32_t* s_c, u64* s_b, xsk_gpu_stats* stats) {
     const u64 um = __ballot(unsent);
     u64 b = 0;
-    if (um) {  // wave-uniform
-        b = unsent ? (u64)len : 0ull;
-        for (int o = 32; o > 0; o >>= 1) b += __shfl_xor(b, o, 64);
-    }
-    if (lane_id() == 0) {
-        s_c[wave_id()] = (uint32_t)__popcll(um);
-        s_b[wave_id()] = b;
+    if (um) b = cp_wave_sum(unsent ? (u64)len : 0ull);  // wave-uniform
+    if (cp_lane() == 0) {
+        s_c[cp_wave()] = (uint32_t)__popcll(um);
+        s_b[cp_wave()] = b;
     }
     __syncthreads();
-    if (wave_id() == 0) {
-        uint32_t c = lane_id() < NW ? s_c[lane_id()] : 0u;
-        u64 t = lane_id() < NW ? s_b[lane_id()] : 0ull;
+    if (cp_wave() == 0) {
+        uint32_t c = cp_lane() < NW ? s_c[cp_lane()] : 0u;
+        u64 t = cp_lane() < NW ? s_b[cp_lane()] : 0ull;
         for (int o = 32; o > 0; o >>= 1) {
             c += __shfl_xor(c, o, 64);
             t += __shfl_xor(t, o, 64);
         }
-        if (lane_id() == 0 && c) {
+        if (cp_lane() == 0 && c) {
             atomicAdd((u64*)&stats->tx_packets, 0ull - (u64)c);
             atomicAdd((u64*)&stats->tx_bytes, 0ull - t);
         }
@@ -114,20 +79,14 @@ __device__ __forceinline__ uint32_t scatter_wg(const xsk_gpu_desc* __restrict__ 
     __shared__ uint32_t s_w[NW];
     __shared__ uint32_t s_c[NW];
     __shared__ u64 s_b[NW];
-    const uint32_t lane = lane_id(), w = wave_id();
+    const uint32_t lane = cp_lane(), w = cp_wave();  // (ahead of the loads: the order the kernels were built from)
     uint4 d;
-    const bool reply = load_frame(descs, verdicts, i, in.n, &d);
-    const u64 m = __ballot(reply);
-    if (lane == 0) s_w[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t base = off, total = off;
-    for (uint32_t k = 0; k < NW; ++k) {
-        const uint32_t c = s_w[k];
-        base += k < w ? c : 0u;
-        total += c;
-    }
-    const uint32_t r_below = base + below(m, lane);
-    if (i < in.n) store_frame(d, reply, i, r_below, in.room, tx, free_list);
+    const bool reply = eg_load_frame(descs, verdicts, i, 0u, in.n, &d);
+    const u64 m = cp_wg_ballot(reply, s_w);
+    uint32_t total = off;
+    for (uint32_t k = 0; k < NW; ++k) total += s_w[k];
+    const uint32_t r_below = cp_waves_below<NW>(s_w, w, off) + cp_below(m, lane);
+    if (i < in.n) eg_store_frame(d, eg_slot(reply, i, r_below, in.room), tx, free_list);
     if (stats && total > off && total > in.room)  // workgroup-uniform: a reply of this workgroup lies past the room
         take_back<NW>(eg_unsent(reply, r_below, in.room), d.z, s_c, s_b, stats);
     return total;
@@ -140,7 +99,7 @@ __global__ __launch_bounds__(kEgSmallThreads) void egress_small_kernel(
     xsk_gpu_egress_counts* __restrict__ counts, xsk_gpu_stats* stats) {
     const EgIn in = eg_prologue(d_n, n_max, d_room);
     const uint32_t total = scatter_wg<kEgSmallThreads / kEgWave>(descs, verdicts, threadIdx.x, in, 0u, tx, free_list, stats);
-    if (threadIdx.x == 0) store_counts(counts, eg_counts(in.n, total, in.room));
+    if (threadIdx.x == 0) eg_store_counts(counts, eg_counts(in.n, total, in.room));
 }
 
 // ---- larger batches, stage 1: per-workgroup reply counts (a workgroup past n writes 0) ----
@@ -152,14 +111,11 @@ __global__ __launch_bounds__(kEgFrames) void egress_count_kernel(const uint8_t* 
     const uint32_t n = eg_count(d_n != nullptr, d_n ? *d_n : 0u, n_max);
     const uint32_t t = threadIdx.x;
     const bool reply = t < eg_wg_frames(n, blockIdx.x) && verdicts[(size_t)blockIdx.x * kEgFrames + t] == XSK_GPU_TX_REPLY;
-    const u64 m = __ballot(reply);
-    if (lane_id() == 0) s_w[wave_id()] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (t == 0) wg_count[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    cp_wg_count(reply, s_w, wg_count);
 }
 
 // ---- stage 2: exclusive scan of the nwg counts in place, and the batch's counts (one workgroup of 1024; thread t owns
-// a contiguous run of the counts, xsk_classify.hip's scan) ----
+// a contiguous run of the counts: cp_scan_cells) ----
 __global__ __launch_bounds__(kEgScanThreads) void egress_scan_kernel(uint32_t* __restrict__ wg_count, uint32_t nwg,
                                                                      const uint32_t* __restrict__ d_n, uint32_t n_max,
                                                                      const uint32_t* __restrict__ d_room,
@@ -167,26 +123,9 @@ __global__ __launch_bounds__(kEgScanThreads) void egress_scan_kernel(uint32_t* _
     __shared__ uint32_t s[kEgScanThreads];
     const EgIn in = eg_prologue(d_n, n_max, d_room);
     uint32_t b, e;
-    eg_scan_run(nwg, threadIdx.x, &b, &e);
-    uint32_t sum = 0;
-    for (uint32_t j = b; j < e; ++j) sum += wg_count[j];
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < kEgScanThreads; o <<= 1) {  // Hillis-Steele inclusive scan
-        const uint32_t v = threadIdx.x >= o ? s[threadIdx.x - o] : 0u;
-        __syncthreads();
-        s[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = s[threadIdx.x] - sum;  // exclusive prefix of this run
-    for (uint32_t j = b; j < e; ++j) {
-        const uint32_t c = wg_count[j];
-        wg_count[j] = run;
-        run += c;
-    }
-    if (threadIdx.x == kEgScanThreads - 1u) {
-        store_counts(counts, eg_counts(in.n, s[kEgScanThreads - 1u], in.room));
-    }
+    cp_scan_run(nwg, threadIdx.x, &b, &e);
+    const uint32_t total = cp_scan_cells(wg_count, b, e, s, cp_put_before);
+    if (threadIdx.x == kEgScanThreads - 1u) eg_store_counts(counts, eg_counts(in.n, total, in.room));
 }
 
 // ---- stage 3: the in-order scatter of both lists ----
@@ -226,7 +165,7 @@ int xsk_gpu_egress_dev(const struct xsk_gpu_desc* d_descs, const uint8_t* d_verd
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    const uint32_t nwg = eg_nwg(n_max);
+    const uint32_t nwg = cp_nwg(n_max);
     uint32_t* wg = (uint32_t*)d_workspace;
     egress_count_kernel<<<dim3(nwg), dim3(kEgFrames), 0, s>>>(d_verdicts, d_n, n_max, wg);
     HIP_TRY(hipGetLastError());

@@ -87,7 +87,7 @@ XSK_EG_FN uint32_t ep_prefix_at(const uint32_t* s_w, const uint64_t* s_m, uint32
 }
 
 // ---- the three-stage path (n_max > kEgSmallMax) ----
-// Grid of stages 1 and 3: eg_nwg(n_max) workgroups of kEgFrames frames; workgroup wg takes part iff it holds a position
+// Grid of stages 1 and 3: cp_nwg(n_max) workgroups of kEgFrames frames; workgroup wg takes part iff it holds a position
 // of [lo, hi).
 XSK_EG_FN bool ep_wg_live(uint32_t wg, uint32_t lo, uint32_t hi) {
     const uint64_t b = (uint64_t)wg * kEgFrames;
@@ -122,10 +122,10 @@ XSK_EG_FN uint32_t ep_carry_begin(uint32_t o) { return o / kEgFrames + (o % kEgF
 // Workspace: words [0, nwg) the per-workgroup reply counts, then their exclusive offsets; words [nwg, nwg + n_ports + 1)
 // the boundary prefixes G(o_p); from ep_part_offset() on nwg records EpPart.  None on the small path.
 XSK_EG_FN size_t ep_part_offset(uint32_t n_max, uint32_t n_ports) {
-    return ((size_t)eg_nwg(n_max) + n_ports + 1u) * sizeof(uint32_t);
+    return ((size_t)cp_nwg(n_max) + n_ports + 1u) * sizeof(uint32_t);
 }
 XSK_EG_FN size_t ep_workspace_bytes(uint32_t n_max, uint32_t n_ports) {
-    return n_max <= kEgSmallMax ? (size_t)0 : ep_part_offset(n_max, n_ports) + (size_t)eg_nwg(n_max) * sizeof(EpPart);
+    return n_max <= kEgSmallMax ? (size_t)0 : ep_part_offset(n_max, n_ports) + (size_t)cp_nwg(n_max) * sizeof(EpPart);
 }
 
 }  // namespace xskgpu

@@ -7,9 +7,10 @@
 // Two paths, the arithmetic of both in xsk_egress_ports.h (host and device):
 //   n_max <= 1024: one launch of one 1024-thread workgroup -- lane per frame, wave ballots, sixteen counts and masks in
 //                  LDS, the prefix at every port boundary from them;
-//   larger:        three launches -- per-workgroup reply counts, one scan (which also takes the prefix at each of the
-//                  n_ports + 1 boundaries, a wave per boundary, and writes d_counts), the in-order scatter -- and, only
-//                  with d_port_stats, a fourth that adds up the scatter's per-workgroup sums, a workgroup per port.
+//   larger:        the three launches of the compaction core (xsk_compact.h) -- per-workgroup reply counts, one scan
+//                  (which also takes the prefix at each of the n_ports + 1 boundaries, a wave per boundary, and writes
+//                  d_counts), the in-order scatter -- and, only with d_port_stats, a fourth that adds up the scatter's
+//                  per-workgroup sums, a workgroup per port.
 // Every kernel stages the offsets (a wave's max-scan of the words, then the clamp) and the rooms into LDS in a prologue.
 // A frame's slot is R_p(i) = G(i) - G(o_p) below its port's start: no atomic hands out a slot, no workgroup waits on
 // another.  HBM / latency bound: 17 B in and at most 16 B out per frame, no frame byte touched, no MFMA.
@@ -44,18 +45,14 @@ struct EpAcc {
     uint32_t n[kEpMaxPorts], n_tx[kEpMaxPorts], n_unsent[kEpMaxPorts];
 };
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kEgWave - 1u); }
-__device__ __forceinline__ uint32_t wave_id() { return threadIdx.x / kEgWave; }
-__device__ __forceinline__ uint32_t below(u64 m, uint32_t lane) { return (uint32_t)__popcll(m & ((1ull << lane) - 1ull)); }
-
 // The prologue (wave 0; the caller's next barrier publishes it): lane l takes word l, an inclusive max-scan over the
 // wave leaves max(d_off[0..l]), the clamp makes it o_l; with 64 ports lane 63 adds the 65th word.  Only
 // d_off[0, n_ports] and d_room[0, n_ports) are read.
 template <bool ROOMS>
 __device__ __forceinline__ void ep_stage(const uint32_t* __restrict__ d_off, uint32_t n_ports, uint32_t n_max,
                                          const uint32_t* __restrict__ d_room, EpLds* s) {
-    if (wave_id() != 0) return;
-    const uint32_t l = lane_id();
+    if (cp_wave() != 0) return;
+    const uint32_t l = cp_lane();
     uint32_t w = l <= n_ports ? d_off[l] : 0u;
     for (uint32_t d = 1; d < kEgWave; d <<= 1) {
         const uint32_t v = __shfl_up(w, d, kEgWave);
@@ -72,28 +69,6 @@ __device__ __forceinline__ void acc_zero(EpAcc* a) {
         a->bytes[t] = a->tx_bytes[t] = a->unsent_bytes[t] = 0ull;
         a->n[t] = a->n_tx[t] = a->n_unsent[t] = 0u;
     }
-}
-
-// Position i: the descriptor as one 16-B load, the verdict as a byte (any alignment).  Nothing outside [lo, hi) is read.
-__device__ __forceinline__ bool load_frame(const xsk_gpu_desc* __restrict__ descs, const uint8_t* __restrict__ verdicts,
-                                           uint32_t i, uint32_t lo, uint32_t hi, uint4* d) {
-    *d = make_uint4(0u, 0u, 0u, 0u);
-    if (!ep_in(i, lo, hi)) return false;
-    *d = reinterpret_cast<const uint4*>(descs)[i];
-    return verdicts[i] == XSK_GPU_TX_REPLY;
-}
-
-// *d_counts is only 4-B aligned: four word stores.
-__device__ __forceinline__ void store_counts(xsk_gpu_egress_counts* __restrict__ counts, const EgCounts& c) {
-    counts->n = c.n;
-    counts->n_tx = c.n_tx;
-    counts->n_tx_full = c.n_tx_full;
-    counts->n_free = c.n_free;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kEgWave);
-    return v;
 }
 
 // A lane's frame i with g_i = G(i): its owner from the staged offsets, its slot, the store ({ addr, len, 0 } as one 16-B
@@ -113,10 +88,7 @@ __device__ __forceinline__ void ep_finish(const uint4& d, bool reply, uint32_t i
     if (ow.on) {
         const uint32_t o_p = s->o[ow.port], g_p = s->g[ow.port], room = s->room[ow.port];
         const EgSlot sl = ep_slot(reply, i, o_p, g_i, g_p, room);
-        if (sl.tx)
-            reinterpret_cast<uint4*>(tx)[sl.slot] = make_uint4(d.x, d.y, d.z, 0u);  // options = 0, as xsk_gpu__rx_emit()
-        else
-            reinterpret_cast<uint2*>(free_list)[sl.slot] = make_uint2(d.x, d.y);
+        eg_store_frame(d, sl, tx, free_list);
         sub = sl.tx;
         uns = ep_unsent(reply, g_i, g_p, room);
     }
@@ -128,10 +100,10 @@ __device__ __forceinline__ void ep_finish(const uint4& d, bool reply, uint32_t i
         if (k0 != 0xFFFFFFFFu && (port_stats || mu)) {  // wave-uniform
             const u64 ms = __ballot(sub);
             u64 b = 0, bt = 0, bu = 0;
-            if (port_stats) b = wave_sum((u64)d.z);
-            if (port_stats && ms) bt = wave_sum(sub ? (u64)d.z : 0ull);
-            if (mu) bu = wave_sum(uns ? (u64)d.z : 0ull);
-            if (lane_id() == 0) {
+            if (port_stats) b = cp_wave_sum((u64)d.z);
+            if (port_stats && ms) bt = cp_wave_sum(sub ? (u64)d.z : 0ull);
+            if (mu) bu = cp_wave_sum(uns ? (u64)d.z : 0ull);
+            if (cp_lane() == 0) {
                 if (port_stats) {
                     atomicAdd(&acc->n[k0], kEgWave);
                     atomicAdd(&acc->bytes[k0], b);
@@ -161,8 +133,8 @@ __device__ __forceinline__ void ep_finish(const uint4& d, bool reply, uint32_t i
         }
     }
     __syncthreads();
-    if (wave_id() != 0) return;
-    const uint32_t p = lane_id();
+    if (cp_wave() != 0) return;
+    const uint32_t p = cp_lane();
     uint32_t nu = 0, carry = 0xFFFFFFFFu;
     u64 bu = 0;
     if (part && port_stats && ep_wg_carries(wg, s->o[0], s->o[n_ports]))  // wave-uniform
@@ -191,8 +163,8 @@ __device__ __forceinline__ void ep_finish(const uint4& d, bool reply, uint32_t i
         }
     }
     if (stats) {
-        const u64 c = wave_sum((u64)nu);
-        const u64 t = wave_sum(bu);
+        const u64 c = cp_wave_sum((u64)nu);
+        const u64 t = cp_wave_sum(bu);
         if (p == 0 && c) {
             atomicAdd((u64*)&stats->tx_packets, 0ull - c);
             atomicAdd((u64*)&stats->tx_bytes, 0ull - t);
@@ -216,17 +188,17 @@ __global__ __launch_bounds__(kEgSmallThreads) void egress_ports_small_kernel(
     acc_zero(&acc);
     __syncthreads();
     uint4 d;
-    const bool reply = load_frame(descs, verdicts, t, s.o[0], s.o[n_ports], &d);
+    const bool reply = eg_load_frame(descs, verdicts, t, s.o[0], s.o[n_ports], &d);
     const u64 m = __ballot(reply);
-    if (lane_id() == 0) {
-        s_w[wave_id()] = (uint32_t)__popcll(m);
-        s_m[wave_id()] = m;
+    if (cp_lane() == 0) {
+        s_w[cp_wave()] = (uint32_t)__popcll(m);
+        s_m[cp_wave()] = m;
     }
     __syncthreads();
     if (t <= n_ports) s.g[t] = ep_prefix_at(s_w, s_m, NW, s.o[t]);  // G at every boundary (o_p <= 1024: all NW waves)
     const uint32_t g_i = ep_prefix_at(s_w, s_m, NW, t);
     __syncthreads();
-    if (t < n_ports) store_counts(counts + t, ep_counts(s.o[t], s.o[t + 1u], s.g[t], s.g[t + 1u], s.room[t]));
+    if (t < n_ports) eg_store_counts(counts + t, ep_counts(s.o[t], s.o[t + 1u], s.g[t], s.g[t + 1u], s.room[t]));
     ep_finish(d, reply, t, g_i, &s, n_ports, tx, free_list, stats, port_stats, &acc, nullptr, 0u);
 }
 
@@ -242,14 +214,11 @@ __global__ __launch_bounds__(kEgFrames) void egress_ports_count_kernel(const uin
     __syncthreads();
     const uint32_t i = blockIdx.x * kEgFrames + threadIdx.x;
     const bool reply = ep_in(i, s.o[0], s.o[n_ports]) && verdicts[i] == XSK_GPU_TX_REPLY;
-    const u64 m = __ballot(reply);
-    if (lane_id() == 0) s_w[wave_id()] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) wg_count[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    cp_wg_count(reply, s_w, wg_count);
 }
 
-// ---- stage 2: exclusive scan of the nwg counts in place (one workgroup of 1024; thread t owns a contiguous run, as
-// xsk_egress.hip's scan), then the prefix at each boundary -- a wave per boundary in turn: the scanned count of the
+// ---- stage 2: exclusive scan of the nwg counts in place (one workgroup of 1024; thread t owns a contiguous run:
+// cp_scan_cells), then the prefix at each boundary -- a wave per boundary in turn: the scanned count of the
 // boundary's workgroup plus the replies among the at most 255 verdicts in front of it -- into ws[nwg + p], and
 // d_counts[p] from their differences ----
 __global__ __launch_bounds__(kEgScanThreads) void egress_ports_scan_kernel(
@@ -261,26 +230,11 @@ __global__ __launch_bounds__(kEgScanThreads) void egress_ports_scan_kernel(
     const uint32_t t = threadIdx.x;
     ep_stage<true>(d_off, n_ports, n_max, d_room, &s);
     uint32_t b, e;
-    eg_scan_run(nwg, t, &b, &e);
-    uint32_t sum = 0;
-    for (uint32_t j = b; j < e; ++j) sum += ws[j];
-    sc[t] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < kEgScanThreads; o <<= 1) {  // Hillis-Steele inclusive scan
-        const uint32_t v = t >= o ? sc[t - o] : 0u;
-        __syncthreads();
-        sc[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = sc[t] - sum;  // exclusive prefix of this run
-    for (uint32_t j = b; j < e; ++j) {
-        const uint32_t c = ws[j];
-        ws[j] = run;
-        run += c;
-    }
+    cp_scan_run(nwg, t, &b, &e);
+    cp_scan_cells(ws, b, e, sc, cp_put_before);  // (its total is read behind the barrier, with the staged offsets)
     __syncthreads();  // the offsets just written are read below by other waves of this workgroup
-    const uint32_t total = sc[kEgScanThreads - 1u], lo = s.o[0], lane = lane_id();
-    for (uint32_t k = wave_id(); k <= n_ports; k += kEgScanThreads / kEgWave) {  // wave-uniform
+    const uint32_t total = sc[kEgScanThreads - 1u], lo = s.o[0], lane = cp_lane();
+    for (uint32_t k = cp_wave(); k <= n_ports; k += kEgScanThreads / kEgWave) {  // wave-uniform
         const uint32_t o = s.o[k], wg = ep_bound_wg(o);
         uint32_t g = total;
         if (wg < nwg) {
@@ -298,7 +252,7 @@ __global__ __launch_bounds__(kEgScanThreads) void egress_ports_scan_kernel(
     }
     __syncthreads();
     if (t <= n_ports) ws[nwg + t] = s.g[t];
-    if (t < n_ports) store_counts(counts + t, ep_counts(s.o[t], s.o[t + 1u], s.g[t], s.g[t + 1u], s.room[t]));
+    if (t < n_ports) eg_store_counts(counts + t, ep_counts(s.o[t], s.o[t + 1u], s.g[t], s.g[t + 1u], s.room[t]));
 }
 
 // ---- stage 3: the in-order scatter of every port's two lists ----
@@ -319,12 +273,10 @@ __global__ __launch_bounds__(kEgFrames) void egress_ports_scatter_kernel(
     if (!ep_wg_live(blockIdx.x, s.o[0], s.o[n_ports])) return;  // workgroup-uniform
     const uint32_t i = blockIdx.x * kEgFrames + t;
     uint4 d;
-    const bool reply = load_frame(descs, verdicts, i, s.o[0], s.o[n_ports], &d);
-    const u64 m = __ballot(reply);
-    if (lane_id() == 0) s_w[wave_id()] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t g_i = ws[blockIdx.x] + below(m, lane_id());
-    for (uint32_t k = 0; k < NW; ++k) g_i += k < wave_id() ? s_w[k] : 0u;
+    const bool reply = eg_load_frame(descs, verdicts, i, s.o[0], s.o[n_ports], &d);
+    const u64 m = cp_wg_ballot(reply, s_w);
+    uint32_t g_i = ws[blockIdx.x] + cp_below(m, cp_lane());
+    for (uint32_t k = 0; k < NW; ++k) g_i += k < cp_wave() ? s_w[k] : 0u;  // (cp_waves_below here builds other code)
     ep_finish(d, reply, i, g_i, &s, n_ports, tx, free_list, stats, port_stats, &acc, part, blockIdx.x);
 }
 
@@ -348,15 +300,15 @@ __global__ __launch_bounds__(kEgFrames) void egress_ports_sum_kernel(const uint3
         bytes += ep_u64(r->bytes_lo, r->bytes_hi);
         tx_bytes += ep_u64(r->tx_bytes_lo, r->tx_bytes_hi);
     }
-    n = wave_sum(n);
-    n_tx = wave_sum(n_tx);
-    bytes = wave_sum(bytes);
-    tx_bytes = wave_sum(tx_bytes);
-    if (lane_id() == 0) {
-        s_r[wave_id()][0] = n;
-        s_r[wave_id()][1] = n_tx;
-        s_r[wave_id()][2] = bytes;
-        s_r[wave_id()][3] = tx_bytes;
+    n = cp_wave_sum(n);
+    n_tx = cp_wave_sum(n_tx);
+    bytes = cp_wave_sum(bytes);
+    tx_bytes = cp_wave_sum(tx_bytes);
+    if (cp_lane() == 0) {
+        s_r[cp_wave()][0] = n;
+        s_r[cp_wave()][1] = n_tx;
+        s_r[cp_wave()][2] = bytes;
+        s_r[cp_wave()][3] = tx_bytes;
     }
     __syncthreads();
     if (threadIdx.x < 4u) {
@@ -398,7 +350,7 @@ int xsk_gpu_egress_ports_dev(const struct xsk_gpu_desc* d_descs, const uint8_t* 
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    const uint32_t nwg = eg_nwg(n_max);
+    const uint32_t nwg = cp_nwg(n_max);
     uint32_t* ws = (uint32_t*)d_workspace;
     EpPart* part = (EpPart*)((char*)d_workspace + ep_part_offset(n_max, n_ports));
     egress_ports_count_kernel<<<dim3(nwg), dim3(kEgFrames), 0, s>>>(d_verdicts, d_off, n_ports, n_max, ws);

@@ -21,15 +21,16 @@
 
 #include "../../include/xsk_gpu.h"
 #include "xsk_classify_wire.h"
+#include "xsk_compact.h"
 
 #define XSK_ST_FN XSK_CW_FN
 
 namespace xskgpu {
 
-constexpr uint32_t kStWave = 64;
-constexpr uint32_t kStFrames = 256;        // frames (and threads) per workgroup of the classify and scatter stages
-constexpr uint32_t kStWaves = kStFrames / kStWave;
-constexpr uint32_t kStScanThreads = 1024;  // a scan workgroup: one per port, over that port's row
+constexpr uint32_t kStWave = kCpWave;
+constexpr uint32_t kStFrames = kCpFrames;  // frames (and threads) per workgroup of the classify and scatter stages
+constexpr uint32_t kStWaves = kCpWaves;
+constexpr uint32_t kStScanThreads = kCpScanThreads;  // a scan workgroup: one per port, over that port's row
 constexpr uint32_t kStMaxPorts = XSK_GPU_STEER_MAX_PORTS;
 constexpr uint32_t kStMaxEntries = XSK_GPU_STEER_MAX_ENTRIES;
 constexpr uint32_t kStPass = XSK_GPU_STEER_PASS;
@@ -210,19 +211,11 @@ XSK_ST_FN StVerdict st_steer_one(const uint8_t* umem, uint64_t umem_size, const 
 // row's total instead, and stage 3 turns the n_ports totals into the rows' starts: d_off.  A frame's slot is then
 // d_off[port], its workgroup's cell, the counts of the lower waves of the workgroup and the rank among the lower lanes
 // of the wave.
-XSK_ST_FN uint32_t st_nwg(uint32_t n) { return n / kStFrames + (n % kStFrames ? 1u : 0u); }
 XSK_ST_FN size_t st_cell(uint32_t port, uint32_t wg, uint32_t nwg) { return (size_t)port * nwg + wg; }
 XSK_ST_FN size_t st_cells(uint32_t n_ports, uint32_t nwg) { return (size_t)n_ports * nwg; }
 
-// The scan of one row of nwg cells: thread t owns the cells [t * per, min(t * per + per, nwg)) of the row.
-XSK_ST_FN uint32_t st_scan_per(uint32_t nwg) { return nwg / kStScanThreads + (nwg % kStScanThreads ? 1u : 0u); }
-XSK_ST_FN void st_scan_run(uint32_t nwg, uint32_t t, uint32_t* b, uint32_t* e) {
-    const uint64_t per = st_scan_per(nwg), lo = t * per, hi = lo + per;
-    *b = (uint32_t)(lo < nwg ? lo : nwg);
-    *e = (uint32_t)(hi < nwg ? hi : nwg);
-}
-
-// What stage 2 leaves in cell j of a row (exclusive prefix `before`, row total `total`), and what stage 3 reads back
+// What stage 2 (cp_scan_cells over a row of cp_nwg(n) cells) leaves in cell j (exclusive prefix `before`, row total
+// `total`), and what stage 3 reads back
 // as workgroup wg's offset inside the row.
 XSK_ST_FN uint32_t st_scanned_cell(uint32_t j, uint32_t before, uint32_t total) { return j == 0u ? total : before; }
 XSK_ST_FN uint32_t st_cell_offset(uint32_t wg, uint32_t cell) { return wg == 0u ? 0u : cell; }
@@ -233,7 +226,7 @@ XSK_ST_FN uint32_t st_slot(uint32_t port_start, uint32_t in_row, uint32_t lower_
 }
 
 XSK_ST_FN size_t st_workspace_bytes(uint32_t n, uint32_t n_ports) {
-    return st_cells(n_ports, st_nwg(n)) * sizeof(uint32_t);
+    return st_cells(n_ports, cp_nwg(n)) * sizeof(uint32_t);
 }
 
 }  // namespace xskgpu

@@ -4,7 +4,7 @@
 // looked up in a sorted table of at most 1024 entries, and the REDIRECT descriptors leave as a stable partition by
 // port.  xsk_gpu_ingress_steer_dev() puts the indirect-count transform behind it on the same stream.
 //
-// Three launches, the filter's compaction (xsk_classify.hip) with a port dimension; the decision and every index in
+// Three launches, the compaction core (xsk_compact.h) with a port dimension; the decision and every index in
 // xsk_steer.h (host and device).  All HBM / latency bound, no MFMA:
 //   1. classify: the table staged once per workgroup into LDS as big-endian dwords (at most 24 KiB, dynamic: none with
 //      an empty table), a lane per frame -- descriptor, the filter's two round trips with the destination riding in
@@ -32,15 +32,12 @@ namespace {
 
 typedef unsigned long long u64;
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kStWave - 1u); }
-__device__ __forceinline__ uint32_t wave_id() { return threadIdx.x / kStWave; }
-
 // The wave's frames by port: one ballot per distinct port present (the port of the lowest lane not yet served, read
 // into a scalar with readlane, which is readfirstlane over the lanes still to do).
 // s_cnt[wave][port] gets the wave's count of every port present -- the rest of the row was zeroed by the caller -- and
 // the lane learns how many lower lanes of its wave carry its port.
 __device__ __forceinline__ uint32_t wave_ranks(bool redirect, uint32_t port, uint32_t (*s_cnt)[kStMaxPorts]) {
-    const uint32_t lane = lane_id(), w = wave_id();
+    const uint32_t lane = cp_lane(), w = cp_wave();
     uint32_t rank = 0;
     u64 todo = __ballot(redirect);
     while (todo) {  // wave-uniform
@@ -81,29 +78,14 @@ __global__ __launch_bounds__(kStFrames) void steer_classify_kernel(
 static_assert(kStWaves == 4 && kStWaves * kStMaxPorts == kStFrames, "the sums and the zeroing above");
 
 // ---- stage 2: a workgroup per port scans that port's row of the matrix in place, exclusive (thread t owns a
-// contiguous run of the row's cells, xsk_classify.hip's scan).  The exclusive value of the cell [p][0] is always 0, so
+// contiguous run of the row's cells: cp_scan_cells).  The exclusive value of the cell [p][0] is always 0, so
 // that cell carries the row's total instead: stage 3 turns the n_ports totals into d_off ----
 __global__ __launch_bounds__(kStScanThreads) void steer_scan_kernel(uint32_t* __restrict__ count, uint32_t nwg) {
     __shared__ uint32_t s[kStScanThreads];
     uint32_t* __restrict__ row = count + st_cell(blockIdx.x, 0u, nwg);
     uint32_t b, e;
-    st_scan_run(nwg, threadIdx.x, &b, &e);
-    uint32_t sum = 0;
-    for (uint32_t j = b; j < e; ++j) sum += row[j];
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < kStScanThreads; o <<= 1) {  // Hillis-Steele inclusive scan
-        const uint32_t v = threadIdx.x >= o ? s[threadIdx.x - o] : 0u;
-        __syncthreads();
-        s[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = s[threadIdx.x] - sum;  // exclusive prefix of this run
-    for (uint32_t j = b; j < e; ++j) {
-        const uint32_t c = row[j];
-        row[j] = st_scanned_cell(j, run, s[kStScanThreads - 1u]);
-        run += c;
-    }
+    cp_scan_run(nwg, threadIdx.x, &b, &e);
+    cp_scan_cells(row, b, e, s, st_scanned_cell);
 }
 
 // ---- stage 3 ----
@@ -143,7 +125,7 @@ __global__ __launch_bounds__(kStFrames) void steer_scatter_kernel(const xsk_gpu_
     __syncthreads();
     if (r) {
         uint32_t lower = 0;
-        for (uint32_t k = 0; k < kStWaves; ++k) lower += k < wave_id() ? s_cnt[k][port] : 0u;
+        for (uint32_t k = 0; k < kStWaves; ++k) lower += k < cp_wave() ? s_cnt[k][port] : 0u;
         const uint32_t in_row = st_cell_offset(blockIdx.x, cell_off[st_cell(port, blockIdx.x, nwg)]);
         reinterpret_cast<uint4*>(out)[st_slot(s_base[port], in_row, lower, rank)] = d;
     }
@@ -181,7 +163,7 @@ int steer_launch(const void* d_umem, uint64_t umem_size, const struct xsk_gpu_de
         if (d_off) HIP_TRY(hipMemsetAsync(d_off, 0, (size_t)(n_ports + 1u) * sizeof(uint32_t), s));
         return 0;
     }
-    const uint32_t nwg = st_nwg(n);
+    const uint32_t nwg = cp_nwg(n);
     uint32_t* cells = (uint32_t*)d_workspace;
     const size_t lds = (size_t)n_entries * kStEntryWords * sizeof(uint32_t);
     steer_classify_kernel<<<dim3(nwg), dim3(kStFrames), lds, s>>>((const uint8_t*)d_umem, umem_size, d_descs, n, opts,
