@@ -938,6 +938,110 @@ int xsk_gpu_rx_step_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_r
 int xsk_gpu_tx_complete_dev(const struct xsk_gpu_ring_dev* comp, const struct xsk_gpu_pool_dev* pool, uint32_t max,
                             uint32_t* d_moved, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The steered RX step (build-added): the RX ring step above with the steering stage inside    */
+/* and one TX ring per port -- from a raw RX ring to up to 64 TX rings in one asynchronous,     */
+/* graph-capturable call with no word to the host.  The reference's loop over  */
+/* its sockets (handle_receive_packets() per struct xsk_socket_info) with every socket's ring   */
+/* in device memory.  One RX ring, fill ring and pool; `tx` is a HOST array of n_ports ring     */
+/* structs, read when the call is made (the kernels receive them by value).  The conventions    */
+/* (used / free / pool_n, masks, what is read when) are those of xsk_gpu_rx_step_dev().         */
+/*                                                                                            */
+/* xsk_gpu_rx_prepare_ports_dev(tx, n_ports, d_plan, d_descs, n_max, d_tx_room, stream): what   */
+/* lies between begin and the steered ingress.  With r = min(d_plan->received, n_max):          */
+/*   d_tx_room[p] = free(tx[p]) for p < n_ports: d_tx_room of xsk_gpu_egress_ports_dev();       */
+/*   d_descs[i] = { addr 0, len 0, options 0 } for r <= i < n_max: the pad descriptor, which    */
+/*     the filter rule of every option word drops (len < 14).  Entries below r are untouched.   */
+/* xsk_gpu_steer_dev(n = n_max) over the padded array redirects exactly the frames it would     */
+/* over the first r: a host-sized call that is exact over a device-side count.  It steers       */
+/* n_max frames however few arrived (the price: DESIGN.md §9.8).                                */
+/*                                                                                            */
+/* xsk_gpu_rx_ports_end_dev(rx, tx, n_ports, pool, d_plan, d_descs, d_actions, d_off, d_tx,     */
+/* d_free, d_counts, n_max, d_res, d_workspace, stream): the ring half, behind                  */
+/* xsk_gpu_egress_ports_dev().  d_descs is begin's array (the steering input), d_actions the    */
+/* steering output over it; d_off, d_tx, d_free, d_counts are those of the egress.  With o_p    */
+/* the clamped running maximum of d_off as there, n_p = o_{p+1} - o_p, c_p = d_counts[p] and    */
+/* r = min(d_plan->received, n_max), total for any content of the words:                        */
+/*   1. per port: t_p = min(c_p.n_tx, n_p, free(tx[p])); TX entry (*tx[p].d_producer + k) &     */
+/*      mask_p = d_tx[o_p + k] for k < t_p, all 16 bytes; *tx[p].d_producer += t_p (no store    */
+/*      when t_p == 0).                                                                        */
+/*   2. the pool, one ordered list: for ascending p, d_free[o_p + j] for j < f_p =              */
+/*      min(c_p.n_free, n_p); then the rest, d_descs[i].addr for every i < r with d_actions[i]  */
+/*      != XSK_GPU_XDP_REDIRECT in batch order (DROP and PASS frames: on no port's list, their  */
+/*      chunks return all the same).  pool_n is read at execution; the first pushed =           */
+/*      min(total, capacity - pool_n) addresses land at d_addr[pool_n + j], the tail is dropped */
+/*      as the host's pool_push() drops it; *d_n_free = pool_n + pushed.                        */
+/*   3. *rx.d_consumer += r (no store when r == 0); *d_res as the struct says (may be NULL).    */
+/*   d_workspace: 16-B aligned, required; for n_max > XSK_GPU_LOWLAT_MAX 8 B per frame and 4 B  */
+/*   per 256 frames (the compacted rest) -- xsk_gpu_rx_step_steer_dev_workspace_size(n_max, 1)  */
+/*   bytes are always enough -- and unused below.                                              */
+/* (Named ports_end, not end_ports: the prefix rx_end is xsk_gpu_rx_end_dev()'s in the export   */
+/* check of tests/test_rx_dev_spec.py.)                                                        */
+/*                                                                                            */
+/* xsk_gpu_rx_step_steer_dev(...): pure composition on one stream, in this order:               */
+/* xsk_gpu_rx_begin_dev(rx, fill, &tx[0], ...) (the plan's tx_room word is port 0's and is not  */
+/* used); prepare; xsk_gpu_ingress_steer_dev(d_umem, ..., d_descs, max_batch, opts, d_table,    */
+/* ..., d_actions, d_ports, d_out, d_off, d_verdicts, NULL, d_stats, ...);                      */
+/* xsk_gpu_egress_ports_dev(d_out, d_verdicts, d_off, n_ports, max_batch, d_tx_room, d_tx,      */
+/* d_free, d_port_counts, d_stats, d_port_stats, ...); end.  d_actions, d_ports (max_batch      */
+/* bytes each) and d_port_counts (n_ports structs) may be NULL: they are then carved from       */
+/* d_workspace (xsk_gpu_rx_step_steer_dev_workspace_size(max_batch, n_ports) bytes, 16-B        */
+/* aligned, zero or garbage) like every other intermediate array.  Entries of d_actions /       */
+/* d_ports at or above `received` hold what the pad gets: DROP, XSK_GPU_STEER_PASS.  The        */
+/* counters are those of the two composed calls: d_stats counts the redirected frames as rx,    */
+/* the egress takes ring-full replies back out of tx; d_port_stats is the per-socket record.    */
+/* PASS frames are freed like DROP frames (a ring for the kernel stack's share is out of        */
+/* scope; d_actions tells which they were).  An empty RX ring changes no ring entry, index      */
+/* word, pool entry or UMEM byte.                                                              */
+/* Identity: with n_ports == 1, n_entries == 0, default_port == 0, d_bound == NULL and a batch  */
+/* the filter redirects whole, the step leaves exactly what xsk_gpu_rx_step_dev() leaves from   */
+/* the same state: rings, index words, pool, d_stats, UMEM.                                    */
+/*                                                                                            */
+/* Checked before any device call, -EINVAL: the rules of every composed call; tx NULL or a      */
+/* tx[p] that is no valid descriptor ring; two ports with the same d_ring or d_producer;        */
+/* n_ports outside [1, 64]; d_tx_room NULL or not 4-B aligned; d_off, d_res, d_port_counts not  */
+/* 4-B aligned; d_actions, d_descs, d_off, d_tx, d_free, d_counts NULL or misaligned in the end */
+/* call; d_workspace NULL or not 16-B aligned; n_max / max_batch outside                        */
+/* [1, XSK_GPU_MAX_BATCH].  Asynchronous on `stream`; the calls allocate nothing, synchronise   */
+/* nothing and read no device memory from the host, so a stream under graph capture may         */
+/* contain them.  Ring protocol order and its limits (no concurrent peer) as above.             */
+/* Kernels (xsk_ring_ports.hip): a bound <= XSK_GPU_LOWLAT_MAX is one launch of one workgroup   */
+/* for prepare and one for end; a larger bound is one grid for prepare and, for end, the count  */
+/* / scan / scatter of the compaction core over the rest list, a copy grid and a one-wave       */
+/* publish launch (lane p stores port p's producer word).                                       */
+/* ------------------------------------------------------------------------------------------ */
+struct xsk_gpu_rx_steer_result {   /* 32 bytes, device memory, 4-B aligned, written not accumulated */
+    uint32_t received;    /* RX entries released                                   */
+    uint32_t redirected;  /* o_{n_ports}: frames on some port's list               */
+    uint32_t replied;     /* sum over ports of entries put on that port's TX ring  */
+    uint32_t tx_full;     /* sum over ports of counts[p].n_tx_full                 */
+    uint32_t refilled;    /* plan.refilled                                         */
+    uint32_t freed;       /* addresses pushed onto the pool                        */
+    uint32_t reserved[2]; /* 0 */
+};
+
+size_t xsk_gpu_rx_step_steer_dev_workspace_size(uint32_t max_batch, uint32_t n_ports);
+
+int xsk_gpu_rx_prepare_ports_dev(const struct xsk_gpu_ring_dev* tx /* n_ports */, uint32_t n_ports,
+                                 const struct xsk_gpu_rx_plan* d_plan, struct xsk_gpu_desc* d_descs, uint32_t n_max,
+                                 uint32_t* d_tx_room /* n_ports */, void* stream);
+
+int xsk_gpu_rx_ports_end_dev(const struct xsk_gpu_ring_dev* rx, const struct xsk_gpu_ring_dev* tx /* n_ports */,
+                             uint32_t n_ports, const struct xsk_gpu_pool_dev* pool,
+                             const struct xsk_gpu_rx_plan* d_plan, const struct xsk_gpu_desc* d_descs,
+                             const uint8_t* d_actions, const uint32_t* d_off, const struct xsk_gpu_desc* d_tx,
+                             const uint64_t* d_free, const struct xsk_gpu_egress_counts* d_counts, uint32_t n_max,
+                             struct xsk_gpu_rx_steer_result* d_res, void* d_workspace, void* stream);
+
+int xsk_gpu_rx_step_steer_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_ring_dev* rx,
+                              const struct xsk_gpu_ring_dev* fill, const struct xsk_gpu_ring_dev* tx /* n_ports */,
+                              const struct xsk_gpu_pool_dev* pool, uint32_t max_batch, uint32_t opts,
+                              const struct xsk_gpu_steer_entry* d_table, uint32_t n_entries, uint32_t default_port,
+                              uint32_t n_ports, const uint64_t* d_bound, uint8_t* d_actions, uint8_t* d_ports,
+                              struct xsk_gpu_egress_counts* d_port_counts, struct xsk_gpu_stats* d_stats,
+                              struct xsk_gpu_stats* d_port_stats, struct xsk_gpu_rx_steer_result* d_res,
+                              void* d_workspace, void* stream);
+
 /* Pipelined RX loop: xsk_gpu_rx_step with up to `depth` batches in flight, so that one queue's steps overlap their
  * PCIe round trips instead of paying one per step.  The object owns up to `depth` contexts of `mode` over one
  * registration of the UMEM and hands batches to them in turn.  A LOWLAT pipe stops adding contexts at the first one

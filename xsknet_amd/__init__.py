@@ -33,6 +33,7 @@ __all__ = [
     "steer_workspace_size", "steer_dev", "ingress_steer_dev",
     "RingDev", "PoolDev", "RxPlan", "rx_begin_dev", "rx_end_dev", "rx_step_dev", "rx_step_dev_workspace_size",
     "tx_complete_dev",
+    "RxSteerResult", "rx_prepare_ports_dev", "rx_end_ports_dev", "rx_step_steer_dev", "rx_step_steer_dev_workspace_size",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -132,7 +133,13 @@ class RxPlan(C.Structure):
                 ("fq_prod", C.c_uint32), ("pool_n", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
-assert C.sizeof(RingDev) == 32 and C.sizeof(PoolDev) == 24 and C.sizeof(RxPlan) == 32
+class RxSteerResult(C.Structure):
+    """struct xsk_gpu_rx_steer_result (device memory): what rx_end_ports_dev / rx_step_steer_dev leave."""
+    _fields_ = [("received", C.c_uint32), ("redirected", C.c_uint32), ("replied", C.c_uint32), ("tx_full", C.c_uint32),
+                ("refilled", C.c_uint32), ("freed", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(RingDev) == 32 and C.sizeof(PoolDev) == 24 and C.sizeof(RxPlan) == 32 and C.sizeof(RxSteerResult) == 32
 
 _lib: Optional[C.CDLL] = None
 
@@ -179,6 +186,13 @@ _SIGS = {
     "xsk_gpu_rx_step_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
                              C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_tx_complete_dev": ([C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, _P, _P], C.c_int),
+    "xsk_gpu_rx_step_steer_dev_workspace_size": ([C.c_uint32, C.c_uint32], C.c_size_t),
+    "xsk_gpu_rx_prepare_ports_dev": ([C.POINTER(RingDev), C.c_uint32, _P, _P, C.c_uint32, _P, _P], C.c_int),
+    "xsk_gpu_rx_ports_end_dev": ([C.POINTER(RingDev), C.POINTER(RingDev), C.c_uint32, C.POINTER(PoolDev), _P, _P, _P, _P,
+                                  _P, _P, _P, C.c_uint32, _P, _P, _P], C.c_int),
+    "xsk_gpu_rx_step_steer_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
+                                   C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                   _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -477,6 +491,50 @@ def tx_complete_dev(comp: RingDev, pool: PoolDev, max_entries: int, moved=None, 
     `moved` (a uint32 word on the device, or None) receives the count."""
     _check("xsk_gpu_tx_complete_dev", lib().xsk_gpu_tx_complete_dev(
         C.byref(comp), C.byref(pool), max_entries, _ptr(moved), _stream_ptr(stream)))
+
+
+def _ring_array(rings):
+    """A host array of struct xsk_gpu_ring_dev from a sequence of RingDev (one TX ring per port)."""
+    return (RingDev * len(rings))(*rings)
+
+
+def rx_step_steer_dev_workspace_size(max_batch: int, n_ports: int) -> int:
+    """xsk_gpu_rx_step_steer_dev_workspace_size: bytes of device workspace rx_step_steer_dev needs for a bound of
+    max_batch frames and n_ports ports (enough for rx_end_ports_dev alone with the same bound)."""
+    return int(lib().xsk_gpu_rx_step_steer_dev_workspace_size(max_batch, n_ports))
+
+
+def rx_prepare_ports_dev(tx, plan, descs, n_max: int, tx_room, stream=None) -> None:
+    """xsk_gpu_rx_prepare_ports_dev: between rx_begin_dev and ingress_steer_dev.  `tx`: a sequence of RingDev, one TX
+    ring per port; tx_room[p] (len(tx) uint32 words on the device) receives port p's ring room, and descs[r:n_max]
+    (r = min(plan.received, n_max)) become the pad descriptor the filter drops, so that steering n_max frames is exact."""
+    _check("xsk_gpu_rx_prepare_ports_dev", lib().xsk_gpu_rx_prepare_ports_dev(
+        _ring_array(tx), len(tx), _ptr(plan), _ptr(descs), n_max, _ptr(tx_room), _stream_ptr(stream)))
+
+
+def rx_end_ports_dev(rx: RingDev, tx, pool: PoolDev, plan, descs, actions, off, tx_list, free, counts, n_max: int,
+                     workspace, res=None, stream=None) -> None:
+    """xsk_gpu_rx_ports_end_dev: behind egress_ports_dev -- port p's span of `tx_list` onto tx[p], every port's free
+    list and then the frames `actions` did not redirect (addresses from `descs`, rx_begin_dev's array) onto the pool,
+    the RX entries released, `res` (one RxSteerResult on the device, 32 bytes, or None) written.  `workspace`: 16-B
+    aligned; rx_step_steer_dev_workspace_size(n_max, 1) bytes are enough."""
+    _check("xsk_gpu_rx_ports_end_dev", lib().xsk_gpu_rx_ports_end_dev(
+        C.byref(rx), _ring_array(tx), len(tx), C.byref(pool), _ptr(plan), _ptr(descs), _ptr(actions), _ptr(off),
+        _ptr(tx_list), _ptr(free), _ptr(counts), n_max, _ptr(res), _ptr(workspace), _stream_ptr(stream)))
+
+
+def rx_step_steer_dev(umem, rx: RingDev, fill: RingDev, tx, pool: PoolDev, max_batch: int, table, n_entries: int,
+                      default_port: int, workspace, bound=None, actions=None, ports=None, port_counts=None, stats=None,
+                      port_stats=None, res=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_rx_step_steer_dev: one steered RX loop iteration over rings, pool and UMEM in device memory -- rx_begin_dev,
+    rx_prepare_ports_dev, ingress_steer_dev, egress_ports_dev, rx_end_ports_dev on one stream, from one RX ring to
+    len(tx) TX rings.  `workspace`: rx_step_steer_dev_workspace_size(max_batch, len(tx)) bytes, 16-B aligned.  `actions`,
+    `ports` (max_batch bytes) and `port_counts` (len(tx) EGRESS_COUNTS_DTYPE) are optional outputs; `stats` /
+    `port_stats`: the shared and the per-port STATS_DTYPE blocks, accumulated; `res`: one RxSteerResult, written."""
+    _check("xsk_gpu_rx_step_steer_dev", lib().xsk_gpu_rx_step_steer_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), _ring_array(tx), C.byref(pool),
+        max_batch, opts, _ptr(table), n_entries, default_port, len(tx), _ptr(bound), _ptr(actions), _ptr(ports),
+        _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res), _ptr(workspace), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,
