@@ -990,8 +990,8 @@ int xsk_gpu_tx_complete_dev(const struct xsk_gpu_ring_dev* comp, const struct xs
 /* d_ports at or above `received` hold what the pad gets: DROP, XSK_GPU_STEER_PASS.  The        */
 /* counters are those of the two composed calls: d_stats counts the redirected frames as rx,    */
 /* the egress takes ring-full replies back out of tx; d_port_stats is the per-socket record.    */
-/* PASS frames are freed like DROP frames (a ring for the kernel stack's share is out of        */
-/* scope; d_actions tells which they were).  An empty RX ring changes no ring entry, index      */
+/* PASS frames are freed like DROP frames (d_actions tells which they were; the step that keeps */
+/* them is xsk_gpu_rx_pass_step_dev() below).  An empty RX ring changes no ring entry, index    */
 /* word, pool entry or UMEM byte.                                                              */
 /* Identity: with n_ports == 1, n_entries == 0, default_port == 0, d_bound == NULL and a batch  */
 /* the filter redirects whole, the step leaves exactly what xsk_gpu_rx_step_dev() leaves from   */
@@ -1041,6 +1041,104 @@ int xsk_gpu_rx_step_steer_dev(void* d_umem, uint64_t umem_size, const struct xsk
                               struct xsk_gpu_egress_counts* d_port_counts, struct xsk_gpu_stats* d_stats,
                               struct xsk_gpu_stats* d_port_stats, struct xsk_gpu_rx_steer_result* d_res,
                               void* d_workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* The steered RX step with a stack ring (build-added): the step above, with    */
+/* the frames the filter passes to the kernel stack (XSK_GPU_XDP_PASS: ARP, TCP, UDP, neighbour */
+/* solicitations, every ICMPv6 type but 128, and with default_port == XSK_GPU_STEER_PASS echo   */
+/* requests to addresses in no table entry) kept instead of freed.  The reference's XDP         */
+/* programs return XDP_PASS for them and the kernel stack gets the packet                      */
+/* (src/kern/inner_xdp.c:38-45); here their descriptors go onto the STACK RING, a descriptor    */
+/* ring in device memory, in batch order, as many as it has room for.  Whoever consumes that    */
+/* ring (a TAP device, an AF_PACKET socket: the caller's) owns the chunks until their addresses */
+/* come back over a completion ring of its own; xsk_gpu_tx_complete_dev(comp, pool, ...) serves */
+/* that side unchanged.                                                                        */
+/*                                                                                            */
+/* `stack`: a descriptor ring (entries struct xsk_gpu_desc, 16-B aligned) or NULL; like the     */
+/* other ring structs host memory, read when the call is made.  Every other parameter has the   */
+/* type and meaning it has in xsk_gpu_rx_ports_end_dev() / xsk_gpu_rx_step_steer_dev().         */
+/*                                                                                            */
+/* xsk_gpu_rx_pass_end_dev(rx, tx, n_ports, stack, pool, d_plan, d_descs, d_actions, d_off,     */
+/* d_tx, d_free, d_counts, n_max, d_res, d_workspace, stream): xsk_gpu_rx_ports_end_dev()'s     */
+/* rule with its step 2 split; total for any content of any word or byte.  With                 */
+/* r = min(d_plan->received, n_max) and, for i < r, nr(i) = d_actions[i] != XSK_GPU_XDP_REDIRECT */
+/* and ps(i) = d_actions[i] == XSK_GPU_XDP_PASS (a byte that is none of 1, 2, 4 is nr and not   */
+/* ps), N(i) / Q(i) = the frames below i with nr / ps set, N = N(r), Q = Q(r):                  */
+/*   1. per port: TX entries and producer words exactly as xsk_gpu_rx_ports_end_dev().          */
+/*   2. the stack ring: room_s = stack ? free(stack) : 0, read at execution; s = min(Q,         */
+/*      room_s); a frame with ps(i) and Q(i) < s becomes stack entry (*stack.d_producer + Q(i)) */
+/*      & mask = d_descs[i], all 16 bytes, `options` as received (the frame is untouched);      */
+/*      *stack.d_producer += s (no store when s == 0).                                         */
+/*   3. the pool, one ordered list: for ascending p the first f_p addresses of port p's free    */
+/*      list as before; then the rest, every i < r with nr(i) that step 2 did not take, in      */
+/*      batch order: d_descs[i].addr at rest position N(i) - min(Q(i), s); n_rest = N - s.      */
+/*      pushed, the dropped tail and *d_n_free as before.                                      */
+/*   4. *rx.d_consumer += r (no store when r == 0).                                            */
+/*   5. *d_res (may be NULL): the six words of xsk_gpu_rx_steer_result, passed = s,             */
+/*      pass_full = Q - s.                                                                     */
+/* A frame on the stack ring is NOT on the pool.  d_stats and d_port_stats are untouched by     */
+/* this: a PASS frame was never counted as rx.                                                 */
+/* Identities: with stack == NULL, or a stack ring with no free entry, the call leaves every    */
+/* ring, index word, pool entry, counter and UMEM byte exactly as xsk_gpu_rx_ports_end_dev() /  */
+/* xsk_gpu_rx_step_steer_dev() leave them from the same state; the first six result words are   */
+/* equal, passed == 0, pass_full == Q.  An empty RX ring changes no ring entry, index word,     */
+/* pool entry or UMEM byte, the stack ring's included.                                         */
+/*   d_workspace: 16-B aligned, required; for n_max > XSK_GPU_LOWLAT_MAX 8 B per frame, two     */
+/*   count rows of 4 B per 256 frames and two totals -- align16(8 * n_max + 2 * 4 *             */
+/*   ceil(n_max / 256) + 8) bytes; xsk_gpu_rx_pass_step_dev_workspace_size(n_max, 1) bytes are  */
+/*   always enough -- and unused below.                                                        */
+/*                                                                                            */
+/* xsk_gpu_rx_pass_step_dev(...): pure composition on one stream, in this order:                */
+/* xsk_gpu_rx_begin_dev, xsk_gpu_rx_prepare_ports_dev, xsk_gpu_ingress_steer_dev,               */
+/* xsk_gpu_egress_ports_dev (the four calls of xsk_gpu_rx_step_steer_dev(), with its            */
+/* arguments), xsk_gpu_rx_pass_end_dev.                                                        */
+/* xsk_gpu_rx_pass_step_dev_workspace_size(max_batch, n_ports): the layout of                   */
+/* xsk_gpu_rx_step_steer_dev_workspace_size() with end's part grown by the second count row and */
+/* its total: for max_batch > XSK_GPU_LOWLAT_MAX that size less align16(8 * max_batch + 4 *     */
+/* ceil(max_batch / 256) + 4) plus align16(8 * max_batch + 8 * ceil(max_batch / 256) + 8); the  */
+/* same size below.                                                                            */
+/*                                                                                            */
+/* Checked before any device call, -EINVAL: every rule of xsk_gpu_rx_ports_end_dev() /          */
+/* xsk_gpu_rx_step_steer_dev(); a non-NULL stack that is no valid descriptor ring (the rules of */
+/* a TX ring); a stack that shares d_ring or d_producer with rx or with any tx[p].              */
+/* Asynchronous on `stream`; the calls allocate nothing, synchronise nothing and read no device */
+/* memory from the host, so a stream under graph capture may contain them.  Ring protocol order */
+/* and its limits (no concurrent peer, no rings in mapped host memory) as above.                */
+/* Kernels (xsk_ring_pass.hip): a bound <= XSK_GPU_LOWLAT_MAX is one launch of one workgroup    */
+/* for end (two ballots per wave rank a frame among the nr and among the ps frames); a larger   */
+/* bound is the count / scan / scatter of the compaction core over two count rows (the scatter  */
+/* stores the stack ring's entries), a copy grid and a one-wave publish launch, the only one    */
+/* that stores an index word.                                                                  */
+/* ------------------------------------------------------------------------------------------ */
+struct xsk_gpu_rx_pass_result {   /* 32 bytes, device memory, 4-B aligned, written not accumulated */
+    uint32_t received;    /* RX entries released                                   */
+    uint32_t redirected;  /* o_{n_ports}: frames on some port's list               */
+    uint32_t replied;     /* sum over ports of entries put on that port's TX ring  */
+    uint32_t tx_full;     /* sum over ports of counts[p].n_tx_full                 */
+    uint32_t refilled;    /* plan.refilled                                         */
+    uint32_t freed;       /* addresses pushed onto the pool                        */
+    uint32_t passed;      /* PASS descriptors put on the stack ring               */
+    uint32_t pass_full;   /* PASS frames freed because the stack ring had no room */
+};
+
+size_t xsk_gpu_rx_pass_step_dev_workspace_size(uint32_t max_batch, uint32_t n_ports);
+
+int xsk_gpu_rx_pass_end_dev(const struct xsk_gpu_ring_dev* rx, const struct xsk_gpu_ring_dev* tx /* n_ports */,
+                            uint32_t n_ports, const struct xsk_gpu_ring_dev* stack /* or NULL */,
+                            const struct xsk_gpu_pool_dev* pool, const struct xsk_gpu_rx_plan* d_plan,
+                            const struct xsk_gpu_desc* d_descs, const uint8_t* d_actions, const uint32_t* d_off,
+                            const struct xsk_gpu_desc* d_tx, const uint64_t* d_free,
+                            const struct xsk_gpu_egress_counts* d_counts, uint32_t n_max,
+                            struct xsk_gpu_rx_pass_result* d_res, void* d_workspace, void* stream);
+
+int xsk_gpu_rx_pass_step_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_ring_dev* rx,
+                             const struct xsk_gpu_ring_dev* fill, const struct xsk_gpu_ring_dev* tx /* n_ports */,
+                             const struct xsk_gpu_ring_dev* stack /* or NULL */, const struct xsk_gpu_pool_dev* pool,
+                             uint32_t max_batch, uint32_t opts, const struct xsk_gpu_steer_entry* d_table,
+                             uint32_t n_entries, uint32_t default_port, uint32_t n_ports, const uint64_t* d_bound,
+                             uint8_t* d_actions, uint8_t* d_ports, struct xsk_gpu_egress_counts* d_port_counts,
+                             struct xsk_gpu_stats* d_stats, struct xsk_gpu_stats* d_port_stats,
+                             struct xsk_gpu_rx_pass_result* d_res, void* d_workspace, void* stream);
 
 /* Pipelined RX loop: xsk_gpu_rx_step with up to `depth` batches in flight, so that one queue's steps overlap their
  * PCIe round trips instead of paying one per step.  The object owns up to `depth` contexts of `mode` over one

@@ -34,6 +34,7 @@ __all__ = [
     "RingDev", "PoolDev", "RxPlan", "rx_begin_dev", "rx_end_dev", "rx_step_dev", "rx_step_dev_workspace_size",
     "tx_complete_dev",
     "RxSteerResult", "rx_prepare_ports_dev", "rx_end_ports_dev", "rx_step_steer_dev", "rx_step_steer_dev_workspace_size",
+    "RxPassResult", "rx_pass_end_dev", "rx_pass_step_dev", "rx_pass_step_dev_workspace_size",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -139,7 +140,14 @@ class RxSteerResult(C.Structure):
                 ("refilled", C.c_uint32), ("freed", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class RxPassResult(C.Structure):
+    """struct xsk_gpu_rx_pass_result (device memory): what rx_pass_end_dev / rx_pass_step_dev leave."""
+    _fields_ = [("received", C.c_uint32), ("redirected", C.c_uint32), ("replied", C.c_uint32), ("tx_full", C.c_uint32),
+                ("refilled", C.c_uint32), ("freed", C.c_uint32), ("passed", C.c_uint32), ("pass_full", C.c_uint32)]
+
+
 assert C.sizeof(RingDev) == 32 and C.sizeof(PoolDev) == 24 and C.sizeof(RxPlan) == 32 and C.sizeof(RxSteerResult) == 32
+assert C.sizeof(RxPassResult) == 32
 
 _lib: Optional[C.CDLL] = None
 
@@ -193,6 +201,12 @@ _SIGS = {
     "xsk_gpu_rx_step_steer_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
                                    C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P,
                                    _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_rx_pass_step_dev_workspace_size": ([C.c_uint32, C.c_uint32], C.c_size_t),
+    "xsk_gpu_rx_pass_end_dev": ([C.POINTER(RingDev), C.POINTER(RingDev), C.c_uint32, C.POINTER(RingDev),
+                                 C.POINTER(PoolDev), _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P], C.c_int),
+    "xsk_gpu_rx_pass_step_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
+                                  C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32,
+                                  C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -535,6 +549,41 @@ def rx_step_steer_dev(umem, rx: RingDev, fill: RingDev, tx, pool: PoolDev, max_b
         _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), _ring_array(tx), C.byref(pool),
         max_batch, opts, _ptr(table), n_entries, default_port, len(tx), _ptr(bound), _ptr(actions), _ptr(ports),
         _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res), _ptr(workspace), _stream_ptr(stream)))
+
+
+def rx_pass_step_dev_workspace_size(max_batch: int, n_ports: int) -> int:
+    """xsk_gpu_rx_pass_step_dev_workspace_size: bytes of device workspace rx_pass_step_dev needs for a bound of max_batch
+    frames and n_ports ports (enough for rx_pass_end_dev alone with the same bound)."""
+    return int(lib().xsk_gpu_rx_pass_step_dev_workspace_size(max_batch, n_ports))
+
+
+def _ring_ref(ring):
+    return None if ring is None else C.byref(ring)
+
+
+def rx_pass_end_dev(rx: RingDev, tx, stack: Optional[RingDev], pool: PoolDev, plan, descs, actions, off, tx_list, free,
+                    counts, n_max: int, workspace, res=None, stream=None) -> None:
+    """xsk_gpu_rx_pass_end_dev: rx_end_ports_dev with a stack ring -- the descriptors of the frames `actions` passes to
+    the kernel stack go onto `stack` (a descriptor RingDev, or None) in batch order, as many as it has room for; only the
+    other frames that were not redirected return to the pool.  `res`: one RxPassResult on the device (32 bytes), or None.
+    `workspace`: 16-B aligned; rx_pass_step_dev_workspace_size(n_max, 1) bytes are enough."""
+    _check("xsk_gpu_rx_pass_end_dev", lib().xsk_gpu_rx_pass_end_dev(
+        C.byref(rx), _ring_array(tx), len(tx), _ring_ref(stack), C.byref(pool), _ptr(plan), _ptr(descs), _ptr(actions),
+        _ptr(off), _ptr(tx_list), _ptr(free), _ptr(counts), n_max, _ptr(res), _ptr(workspace), _stream_ptr(stream)))
+
+
+def rx_pass_step_dev(umem, rx: RingDev, fill: RingDev, tx, stack: Optional[RingDev], pool: PoolDev, max_batch: int, table,
+                     n_entries: int, default_port: int, workspace, bound=None, actions=None, ports=None,
+                     port_counts=None, stats=None, port_stats=None, res=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_rx_pass_step_dev: rx_step_steer_dev with a stack ring -- rx_begin_dev, rx_prepare_ports_dev,
+    ingress_steer_dev, egress_ports_dev, rx_pass_end_dev on one stream.  `stack`: a descriptor RingDev for the frames the
+    filter passes to the kernel stack, or None (then, as with a full ring, the step is rx_step_steer_dev).  `workspace`:
+    rx_pass_step_dev_workspace_size(max_batch, len(tx)) bytes, 16-B aligned; `res`: one RxPassResult, written; the other
+    arguments as in rx_step_steer_dev."""
+    _check("xsk_gpu_rx_pass_step_dev", lib().xsk_gpu_rx_pass_step_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), _ring_array(tx), _ring_ref(stack),
+        C.byref(pool), max_batch, opts, _ptr(table), n_entries, default_port, len(tx), _ptr(bound), _ptr(actions),
+        _ptr(ports), _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res), _ptr(workspace), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,
