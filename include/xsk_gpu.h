@@ -1140,6 +1140,78 @@ int xsk_gpu_rx_pass_step_dev(void* d_umem, uint64_t umem_size, const struct xsk_
                              struct xsk_gpu_stats* d_stats, struct xsk_gpu_stats* d_port_stats,
                              struct xsk_gpu_rx_pass_result* d_res, void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* All completion rings in one call, and the whole loop body (build-added).    */
+/* The reference's handle_receive_packets() ends with complete_tx() (src/lib/xsk_receive.c:236, */
+/* :77-99), which returns the chunks of transmitted frames to the frame stack.  A caller of     */
+/* xsk_gpu_rx_pass_step_dev() at 64 ports owns 65 completion rings, one per socket and the      */
+/* stack consumer's; xsk_gpu_tx_complete_rings_dev() drains them all into the pool by one call, */
+/* and xsk_gpu_rx_loop_dev() is the step and that call on one stream: receive, refill, steer,   */
+/* reply, per-port TX, stack ring, completion, with no word to the host.                        */
+/*                                                                                            */
+/* xsk_gpu_tx_complete_rings_dev(comp, n_rings, pool, max, d_moved, d_pushed, stream).          */
+/* `comp`: n_rings address rings (entries uint64_t, 8-B aligned), a host array read when the    */
+/* call is made; the words and entries are read when the kernels execute.  used / free / pool_n */
+/* with their clamps and entries addressed through the mask as above.  Total for any content of */
+/* any word:                                                                                   */
+/*   pool_n = min(*d_n_free, capacity), room = capacity - pool_n; for ascending q < n_rings     */
+/*     n_q = min(used(comp[q]), max),  A_0 = 0,  p_q = min(n_q, room - A_q),                    */
+/*     A_{q+1} = A_q + p_q      (the running clamp: no sum exceeds capacity, nothing wraps even */
+/*                               at 65 rings of 2^31 entries);                                 */
+/*   d_addr[pool_n + A_q + j] = completion entry (*comp[q].d_consumer + j) & mask_q, j < p_q:   */
+/*     ring order, and inside a ring the ring's own order; what does not fit is dropped, as the */
+/*     host's pool_push() drops it;                                                            */
+/*   *comp[q].d_consumer += n_q (no store when n_q == 0);                                      */
+/*   *d_n_free = pool_n + A_{n_rings}, always stored (a count word above the capacity ends      */
+/*     clamped);                                                                               */
+/*   d_moved[q] = n_q (n_rings words, or NULL);  *d_pushed = A_{n_rings} (one word, or NULL).   */
+/*   max == 0 launches nothing: d_moved[0 .. n_rings) and *d_pushed are zeroed by asynchronous  */
+/*   memsets where given.                                                                      */
+/* Identity: the call leaves every ring entry, index word, pool entry and d_moved word exactly  */
+/* as xsk_gpu_tx_complete_dev(&comp[q], pool, max, d_moved ? &d_moved[q] : NULL, stream) for    */
+/* q = 0 .. n_rings - 1 leaves them from the same state; with n_rings == 1 it is that call.     */
+/* Checked before any device call, -EINVAL: comp NULL; n_rings outside [1,                      */
+/* XSK_GPU_COMPLETE_MAX_RINGS]; a comp[q] that is no valid address ring; two rings that share   */
+/* d_ring or d_consumer; an invalid pool; max > XSK_GPU_MAX_BATCH; d_moved or d_pushed not 4-B  */
+/* aligned.  No workspace.                                                                     */
+/*                                                                                            */
+/* xsk_gpu_rx_loop_dev(...): pure composition on one stream, in the reference's order:          */
+/* xsk_gpu_rx_pass_step_dev() with its 22 arguments, then xsk_gpu_tx_complete_rings_dev(comp,   */
+/* n_comp, pool, complete_max, d_moved, d_pushed, stream).  d_workspace:                        */
+/* xsk_gpu_rx_pass_step_dev_workspace_size(max_batch, n_ports) bytes.  n_comp == 0 (comp,       */
+/* complete_max, d_moved and d_pushed ignored) is xsk_gpu_rx_pass_step_dev() to the byte.       */
+/* Checked before any device call, -EINVAL: every rule of both calls -- those of the completion */
+/* call before the step launches anything -- and a comp[q] that shares d_ring or d_consumer     */
+/* with rx, fill, stack or any tx[p].                                                          */
+/*                                                                                            */
+/* Asynchronous on `stream`; the calls allocate nothing, synchronise nothing and read no device */
+/* memory from the host, so a stream under graph capture may contain them.  Ring protocol order */
+/* and its limits (no concurrent peer, no rings in mapped host memory) as above.                */
+/* Kernels (xsk_ring_complete.hip): max <= XSK_GPU_LOWLAT_MAX is one launch of one 1024-thread  */
+/* workgroup (lane q reads ring q's words, the n_q and the prefix A meet in LDS, the lanes      */
+/* stride over L < A_{n_rings} and find each position's ring by search in A, a fence and a      */
+/* barrier, lane q stores ring q's words); a larger max is a copy grid of 256 entries a         */
+/* workgroup, sized from the sum of min(max, size_q) and capped at 4096 workgroups, and a       */
+/* 128-lane publish launch, the only one that stores a word.                                   */
+/* ------------------------------------------------------------------------------------------ */
+#define XSK_GPU_COMPLETE_MAX_RINGS 65u   /* XSK_GPU_STEER_MAX_PORTS + the stack consumer's */
+
+int xsk_gpu_tx_complete_rings_dev(const struct xsk_gpu_ring_dev* comp /* n_rings, host array */, uint32_t n_rings,
+                                  const struct xsk_gpu_pool_dev* pool, uint32_t max,
+                                  uint32_t* d_moved /* n_rings words or NULL */, uint32_t* d_pushed /* one word or NULL */,
+                                  void* stream);
+
+int xsk_gpu_rx_loop_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_ring_dev* rx,
+                        const struct xsk_gpu_ring_dev* fill, const struct xsk_gpu_ring_dev* tx /* n_ports */,
+                        const struct xsk_gpu_ring_dev* stack /* or NULL */, const struct xsk_gpu_pool_dev* pool,
+                        uint32_t max_batch, uint32_t opts, const struct xsk_gpu_steer_entry* d_table,
+                        uint32_t n_entries, uint32_t default_port, uint32_t n_ports, const uint64_t* d_bound,
+                        uint8_t* d_actions, uint8_t* d_ports, struct xsk_gpu_egress_counts* d_port_counts,
+                        struct xsk_gpu_stats* d_stats, struct xsk_gpu_stats* d_port_stats,
+                        struct xsk_gpu_rx_pass_result* d_res, const struct xsk_gpu_ring_dev* comp /* n_comp */,
+                        uint32_t n_comp, uint32_t complete_max, uint32_t* d_moved, uint32_t* d_pushed,
+                        void* d_workspace, void* stream);
+
 /* Pipelined RX loop: xsk_gpu_rx_step with up to `depth` batches in flight, so that one queue's steps overlap their
  * PCIe round trips instead of paying one per step.  The object owns up to `depth` contexts of `mode` over one
  * registration of the UMEM and hands batches to them in turn.  A LOWLAT pipe stops adding contexts at the first one

@@ -35,6 +35,7 @@ __all__ = [
     "tx_complete_dev",
     "RxSteerResult", "rx_prepare_ports_dev", "rx_end_ports_dev", "rx_step_steer_dev", "rx_step_steer_dev_workspace_size",
     "RxPassResult", "rx_pass_end_dev", "rx_pass_step_dev", "rx_pass_step_dev_workspace_size",
+    "COMPLETE_MAX_RINGS", "tx_complete_rings_dev", "rx_loop_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,6 +76,7 @@ assert EGRESS_COUNTS_DTYPE.itemsize == 16
 STEER_ENTRY_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("port", "u1"), ("pad", "u1", (6,))])
 STEER_PASS, STEER_MAX_PORTS, STEER_MAX_ENTRIES = 0xFF, 64, 1024  # XSK_GPU_STEER_*
 assert STEER_ENTRY_DTYPE.itemsize == 24
+COMPLETE_MAX_RINGS = STEER_MAX_PORTS + 1  # XSK_GPU_COMPLETE_MAX_RINGS: a completion ring per port, and the stack's
 
 
 class XskGpuError(RuntimeError):
@@ -207,6 +209,12 @@ _SIGS = {
     "xsk_gpu_rx_pass_step_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
                                   C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32,
                                   C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_tx_complete_rings_dev": ([C.POINTER(RingDev), C.c_uint32, C.POINTER(PoolDev), C.c_uint32, _P, _P, _P],
+                                      C.c_int),
+    "xsk_gpu_rx_loop_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
+                             C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32,
+                             C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(RingDev), C.c_uint32, C.c_uint32, _P, _P,
+                             _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -584,6 +592,32 @@ def rx_pass_step_dev(umem, rx: RingDev, fill: RingDev, tx, stack: Optional[RingD
         _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), _ring_array(tx), _ring_ref(stack),
         C.byref(pool), max_batch, opts, _ptr(table), n_entries, default_port, len(tx), _ptr(bound), _ptr(actions),
         _ptr(ports), _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res), _ptr(workspace), _stream_ptr(stream)))
+
+
+def tx_complete_rings_dev(comps, pool: PoolDev, max_entries: int, moved=None, pushed=None, stream=None) -> None:
+    """xsk_gpu_tx_complete_rings_dev: tx_complete_dev over every completion ring of `comps` (a sequence of up to
+    COMPLETE_MAX_RINGS address RingDev) in turn, by one call: up to max_entries entries of each ring back onto the pool,
+    in ring order, as many as the pool has room for.  `moved` (len(comps) uint32 words on the device, or None) receives
+    every ring's count, `pushed` (one word, or None) what the pool took."""
+    _check("xsk_gpu_tx_complete_rings_dev", lib().xsk_gpu_tx_complete_rings_dev(
+        _ring_array(comps) if len(comps) else None, len(comps), C.byref(pool), max_entries, _ptr(moved), _ptr(pushed),
+        _stream_ptr(stream)))
+
+
+def rx_loop_dev(umem, rx: RingDev, fill: RingDev, tx, stack: Optional[RingDev], pool: PoolDev, max_batch: int, table,
+                n_entries: int, default_port: int, comps, complete_max: int, workspace, bound=None, actions=None,
+                ports=None, port_counts=None, stats=None, port_stats=None, res=None, moved=None, pushed=None, stream=None,
+                opts: int = 0) -> None:
+    """xsk_gpu_rx_loop_dev: the whole RX loop body over all sockets on one stream -- rx_pass_step_dev, then
+    tx_complete_rings_dev(comps, pool, complete_max, moved, pushed).  `comps`: the completion rings (one per port and the
+    stack consumer's, up to COMPLETE_MAX_RINGS); empty: the call is rx_pass_step_dev.  `workspace`:
+    rx_pass_step_dev_workspace_size(max_batch, len(tx)) bytes, 16-B aligned; the other arguments as in those two calls."""
+    _check("xsk_gpu_rx_loop_dev", lib().xsk_gpu_rx_loop_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), _ring_array(tx), _ring_ref(stack),
+        C.byref(pool), max_batch, opts, _ptr(table), n_entries, default_port, len(tx), _ptr(bound), _ptr(actions),
+        _ptr(ports), _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res),
+        _ring_array(comps) if len(comps) else None, len(comps), complete_max, _ptr(moved), _ptr(pushed),
+        _ptr(workspace), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,

@@ -1,8 +1,9 @@
 // xsk_ring_ports_device.h — what the end kernels of xsk_ring_ports.hip (xsk_gpu_rx_ports_end_dev()) and
 // of xsk_ring_pass.hip (xsk_gpu_rx_pass_end_dev(), §9.9) share: the ring and pool arguments as the kernels take them,
 // the decision a workgroup makes from the words (EndLds, end_decide), the copy (end_copy) and the publish (end_publish),
-// and the argument rules of a ring, a pool, a bound and a set of ports.  Device code and host checks of those two files
-// only; the arithmetic is xsk_ring_ports.h's.  Everything here is in an anonymous namespace: nothing is exported.
+// and the argument rules of a ring, a pool, a bound and a set of ports.  Device code and host checks of those two files,
+// and the ring and pool arguments, load_word and the ring and pool rules for xsk_ring_complete.hip (§9.10); the
+// arithmetic is xsk_ring_ports.h's.  Everything here is in an anonymous namespace: nothing is exported.
 #ifndef XSK_RING_PORTS_DEVICE_H
 #define XSK_RING_PORTS_DEVICE_H
 
