@@ -1212,6 +1212,63 @@ int xsk_gpu_rx_loop_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_r
                         uint32_t n_comp, uint32_t complete_max, uint32_t* d_moved, uint32_t* d_pushed,
                         void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The loop body in one launch (build-added).  At the sizes the loop runs at -- */
+/* the reference's batch is 64 frames, RX_BATCH_SIZE -- xsk_gpu_rx_loop_dev() is a chain of    */
+/* about ten dependent launches of one or four workgroups each, and is bound by them, not by   */
+/* the frames.  xsk_gpu_rx_fused_loop_dev() runs the same stages in ONE launch of one          */
+/* 1024-thread workgroup, behind workgroup barriers where the loop call has kernel boundaries.  */
+/*                                                                                            */
+/* (The name: an existing check of the export table reserves the substring "rx_loop" for       */
+/* xsk_gpu_rx_loop_dev() alone, so the fused call is xsk_gpu_rx_fused_loop_dev; the Python      */
+/* wrapper is rx_loop_fused_dev.)                                                              */
+/*                                                                                            */
+/* xsk_gpu_rx_fused_loop_dev(...): the 27 parameters of xsk_gpu_rx_loop_dev(), in the same      */
+/* order and with the same meaning; d_workspace: xsk_gpu_rx_pass_step_dev_workspace_size(       */
+/* max_batch, n_ports) bytes, 16-B aligned, zero or garbage.  For max_batch in [1,              */
+/* XSK_GPU_LOWLAT_MAX], and with n_comp > 0 also complete_max in [0, XSK_GPU_LOWLAT_MAX], the   */
+/* call is total for any content of any word, and from the same state it leaves exactly what   */
+/* xsk_gpu_rx_loop_dev() leaves:                                                               */
+/*   every ring entry and index word -- RX, fill, the n_ports TX rings, the stack ring, the     */
+/*     n_comp completion rings;                                                                */
+/*   every pool entry and the pool's count word;  every UMEM byte;                             */
+/*   d_actions and d_ports over all max_batch entries when given (entries at or above          */
+/*     `received` hold XSK_GPU_XDP_DROP and XSK_GPU_STEER_PASS);                                */
+/*   d_port_counts, d_stats (accumulated), d_port_stats, *d_res, d_moved[0 .. n_comp), *d_pushed.*/
+/* The content of d_workspace after the call is unspecified: the one thing a caller may not    */
+/* compare.  n_comp == 0 is xsk_gpu_rx_pass_step_dev() to the byte; stack == NULL is the        */
+/* steered step; complete_max == 0 zeroes d_moved[0 .. n_comp) and *d_pushed, as the loop call  */
+/* does (the kernel stores the zeros itself).                                                  */
+/* Checked before any device call, -EINVAL: every rule of xsk_gpu_rx_loop_dev() (both calls     */
+/* check through one function); max_batch > XSK_GPU_LOWLAT_MAX; complete_max >                  */
+/* XSK_GPU_LOWLAT_MAX with n_comp > 0; a ring whose d_ring is at or above 2^56 (no address of   */
+/* this platform is; the kernel takes its rings packed, 24 B each, with log2(size) in the       */
+/* pointer's top byte).                                                                        */
+/*                                                                                            */
+/* Asynchronous on `stream`; the call allocates nothing, synchronises nothing, reads no device */
+/* memory from the host and makes no host-to-device copy (the ring structs are host arrays      */
+/* read when the call is made and travel by value), so a stream under graph capture may contain */
+/* it: one kernel node.  Ring protocol order and its limits as above.                          */
+/* Which call to use (measured): the fused call at the reference's batch of 64 */
+/* frames (0.75 to 0.89 of the loop call's time) and for uniform frames up to the bound's top   */
+/* (1024 x 1500 B: 70 us against 77 us); the loop call for several hundred frames of mixed      */
+/* lengths with wire options (1024 mixed dual-stack frames: 193 us fused against 139 us -- one  */
+/* workgroup streams them through one CU) and for every bound above XSK_GPU_LOWLAT_MAX.         */
+/* Kernel (xsk_loop_fused.hip, xsk_loop_fused_ds.hip): begin, prepare, the one-workgroup form   */
+/* of the steering partition (a lane per frame, a 16 x 64 count matrix in LDS, no atomic hands  */
+/* out a slot), the transform's round body over sub-tiles, egress per port, end, completion.    */
+/* ------------------------------------------------------------------------------------------ */
+int xsk_gpu_rx_fused_loop_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_ring_dev* rx,
+                              const struct xsk_gpu_ring_dev* fill, const struct xsk_gpu_ring_dev* tx /* n_ports */,
+                              const struct xsk_gpu_ring_dev* stack /* or NULL */, const struct xsk_gpu_pool_dev* pool,
+                              uint32_t max_batch, uint32_t opts, const struct xsk_gpu_steer_entry* d_table,
+                              uint32_t n_entries, uint32_t default_port, uint32_t n_ports, const uint64_t* d_bound,
+                              uint8_t* d_actions, uint8_t* d_ports, struct xsk_gpu_egress_counts* d_port_counts,
+                              struct xsk_gpu_stats* d_stats, struct xsk_gpu_stats* d_port_stats,
+                              struct xsk_gpu_rx_pass_result* d_res, const struct xsk_gpu_ring_dev* comp /* n_comp */,
+                              uint32_t n_comp, uint32_t complete_max, uint32_t* d_moved, uint32_t* d_pushed,
+                              void* d_workspace, void* stream);
+
 /* Pipelined RX loop: xsk_gpu_rx_step with up to `depth` batches in flight, so that one queue's steps overlap their
  * PCIe round trips instead of paying one per step.  The object owns up to `depth` contexts of `mode` over one
  * registration of the UMEM and hands batches to them in turn.  A LOWLAT pipe stops adding contexts at the first one

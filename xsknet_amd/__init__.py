@@ -35,7 +35,7 @@ __all__ = [
     "tx_complete_dev",
     "RxSteerResult", "rx_prepare_ports_dev", "rx_end_ports_dev", "rx_step_steer_dev", "rx_step_steer_dev_workspace_size",
     "RxPassResult", "rx_pass_end_dev", "rx_pass_step_dev", "rx_pass_step_dev_workspace_size",
-    "COMPLETE_MAX_RINGS", "tx_complete_rings_dev", "rx_loop_dev",
+    "COMPLETE_MAX_RINGS", "tx_complete_rings_dev", "rx_loop_dev", "rx_loop_fused_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -215,6 +215,10 @@ _SIGS = {
                              C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32,
                              C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(RingDev), C.c_uint32, C.c_uint32, _P, _P,
                              _P, _P], C.c_int),
+    "xsk_gpu_rx_fused_loop_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.POINTER(RingDev),
+                                   C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(RingDev), C.c_uint32, C.c_uint32, _P, _P,
+                                   _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -613,6 +617,21 @@ def rx_loop_dev(umem, rx: RingDev, fill: RingDev, tx, stack: Optional[RingDev], 
     stack consumer's, up to COMPLETE_MAX_RINGS); empty: the call is rx_pass_step_dev.  `workspace`:
     rx_pass_step_dev_workspace_size(max_batch, len(tx)) bytes, 16-B aligned; the other arguments as in those two calls."""
     _check("xsk_gpu_rx_loop_dev", lib().xsk_gpu_rx_loop_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), _ring_array(tx), _ring_ref(stack),
+        C.byref(pool), max_batch, opts, _ptr(table), n_entries, default_port, len(tx), _ptr(bound), _ptr(actions),
+        _ptr(ports), _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res),
+        _ring_array(comps) if len(comps) else None, len(comps), complete_max, _ptr(moved), _ptr(pushed),
+        _ptr(workspace), _stream_ptr(stream)))
+
+
+def rx_loop_fused_dev(umem, rx: RingDev, fill: RingDev, tx, stack: Optional[RingDev], pool: PoolDev, max_batch: int,
+                      table, n_entries: int, default_port: int, comps, complete_max: int, workspace, bound=None,
+                      actions=None, ports=None, port_counts=None, stats=None, port_stats=None, res=None, moved=None,
+                      pushed=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_rx_fused_loop_dev: rx_loop_dev as one launch of one workgroup, for max_batch (and, with completion rings,
+    complete_max) up to LOWLAT_MAX; from the same state it leaves what rx_loop_dev leaves.  Arguments as rx_loop_dev's.
+    (The C symbol keeps clear of "rx_loop", which the export-table checks reserve for xsk_gpu_rx_loop_dev.)"""
+    _check("xsk_gpu_rx_fused_loop_dev", lib().xsk_gpu_rx_fused_loop_dev(
         _ptr(umem), umem.numel() * umem.element_size(), C.byref(rx), C.byref(fill), _ring_array(tx), _ring_ref(stack),
         C.byref(pool), max_batch, opts, _ptr(table), n_entries, default_port, len(tx), _ptr(bound), _ptr(actions),
         _ptr(ports), _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res),

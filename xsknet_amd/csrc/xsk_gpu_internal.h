@@ -74,6 +74,10 @@ XSK_GPU__HIDDEN void xsk_gpu__echo_ds_launch(const void* args, uint32_t grid, ui
 XSK_GPU__HIDDEN void xsk_gpu__echo_ds_indirect_launch(const void* args, const uint32_t* d_n, uint32_t i0, uint32_t len,
                                                       uint32_t grid, void* stream);
 
+/* xsk_loop_fused_ds.hip: launch the dual-stack instance of xsk_gpu_rx_fused_loop_dev()'s kernel (xsk_loop_fused.hip) with
+ * `args`, a LoopFusedArgs; the launch's outcome is left in hipGetLastError(). */
+XSK_GPU__HIDDEN void xsk_gpu__loop_fused_ds_launch(const void* args, void* stream);
+
 /* xsk_echo.hip: xsk_gpu_echo_dev_opts for counters in mapped host memory (no device atomics): d_stats
  * must be a slot zeroed for this call (a one-workgroup launch stores the counters without reading it).
  * tile: frames per wave of a small batch (xsk_gpu__small_tile), 0 = ceil(n / 16). */

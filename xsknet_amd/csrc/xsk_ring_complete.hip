@@ -22,6 +22,7 @@
 #include "../../include/xsk_gpu.h"
 #include "xsk_hip_util.h"
 #include "xsk_ring_complete.h"
+#include "xsk_ring_complete_device.h"
 #include "xsk_ring_ports_device.h"
 
 using namespace xskgpu;
@@ -33,21 +34,8 @@ static_assert(kRcPublish >= kRcMaxRings, "the publish launch has a lane per ring
 
 namespace {
 
-struct CompRings {  // the completion rings, by value in the kernel arguments
-    Ring r[kRcMaxRings];
-};
-static_assert(sizeof(CompRings) + sizeof(Pool) + 4 * 8 <= 4096, "the kernel arguments");
-
-__device__ __forceinline__ uint2* addr_slot(const Ring& r, uint32_t slot) {
-    return reinterpret_cast<uint2*>(r.ring) + slot;
-}
-
-// What one workgroup decides from the words, in LDS.
-struct CompLds {
-    uint32_t n[kRcMaxRings], cons[kRcMaxRings];
-    uint32_t A[kRcMaxBounds];
-    uint32_t pool_n;
-};
+// (CompRings, CompLds, comp_copy, comp_publish and the one-workgroup form,
+// tx_complete_rings_small_body: xsk_ring_complete_device.h)
 
 // Every lane of the workgroup calls it; two barriers.  Lanes walk the rings in strides of the workgroup's size.
 __device__ __forceinline__ void comp_decide(const CompRings& comp, uint32_t n_rings, const Pool& pool, uint32_t max,
@@ -66,42 +54,11 @@ __device__ __forceinline__ void comp_decide(const CompRings& comp, uint32_t n_ri
     __syncthreads();
 }
 
-// The lanes first, first + stride, ...: an address is one 8-B load and store.
-__device__ __forceinline__ void comp_copy(const CompRings& comp, uint32_t n_rings, const Pool& pool, const CompLds* s,
-                                          uint64_t first, uint64_t stride) {
-    const uint32_t total = s->A[n_rings];
-    for (uint64_t L = first; L < total; L += stride) {
-        const RcSrc src = rc_src(s->A, n_rings, (uint32_t)L);
-        const Ring& ring = comp.r[src.ring];
-        reinterpret_cast<uint2*>(pool.addr)[rc_pool_slot(s->pool_n, (uint32_t)L)] =
-            *addr_slot(ring, rc_ring_slot(s->cons[src.ring], src.j, ring.size));
-    }
-}
-
-// Lane q stores ring q's consumer word and d_moved[q]; lane 0 the pool's count and *d_pushed.
-__device__ __forceinline__ void comp_publish(const CompRings& comp, uint32_t n_rings, const Pool& pool, const CompLds* s,
-                                             uint32_t* d_moved, uint32_t* d_pushed) {
-    const uint32_t t = threadIdx.x, nt = blockDim.x;
-    for (uint32_t q = t; q < n_rings; q += nt) {
-        const uint32_t n = s->n[q];
-        if (n) *comp.r[q].cons = rc_cons_after(s->cons[q], n);
-        if (d_moved) d_moved[q] = n;
-    }
-    if (t == 0) {
-        *pool.n_free = rc_pool_after(s->pool_n, s->A[n_rings]);
-        if (d_pushed) *d_pushed = s->A[n_rings];
-    }
-}
-
 __global__ __launch_bounds__(kRcSmallThreads) void tx_complete_rings_small_kernel(CompRings comp, uint32_t n_rings,
                                                                                   Pool pool, uint32_t max,
                                                                                   uint32_t* d_moved, uint32_t* d_pushed) {
     __shared__ CompLds s;
-    comp_decide(comp, n_rings, pool, max, &s);
-    comp_copy(comp, n_rings, pool, &s, threadIdx.x, kRcSmallThreads);
-    __threadfence();  // the entries before the words that cover them
-    __syncthreads();
-    comp_publish(comp, n_rings, pool, &s, d_moved, d_pushed);
+    tx_complete_rings_small_body(comp, n_rings, pool, max, d_moved, d_pushed, &s, comp_decide);
 }
 
 __global__ __launch_bounds__(kRdCopy) void tx_complete_rings_copy_kernel(CompRings comp, uint32_t n_rings, Pool pool,
@@ -119,36 +76,7 @@ __global__ __launch_bounds__(kRcPublish) void tx_complete_rings_publish_kernel(C
     comp_publish(comp, n_rings, pool, &s, d_moved, d_pushed);
 }
 
-// ---- the argument rules ----
-bool shares(const xsk_gpu_ring_dev* a, const xsk_gpu_ring_dev* b) {
-    return a->d_ring == b->d_ring || a->d_consumer == b->d_consumer;
-}
-// n_rings address rings, each valid, no two sharing an entry array or a consumer word; a pool, a bound, two outputs
-bool complete_ok(const xsk_gpu_ring_dev* comp, uint32_t n_rings, const xsk_gpu_pool_dev* pool, uint32_t max,
-                 const uint32_t* d_moved, const uint32_t* d_pushed) {
-    if (!comp || n_rings < 1u || n_rings > kRcMaxRings || !pool_ok(pool) || max > XSK_GPU_MAX_BATCH ||
-        ((uintptr_t)d_moved & 3u) || ((uintptr_t)d_pushed & 3u))
-        return false;
-    for (uint32_t q = 0; q < n_rings; ++q) {
-        if (!ring_ok(comp + q, 8u)) return false;
-        for (uint32_t k = 0; k < q; ++k)
-            if (shares(comp + k, comp + q)) return false;
-    }
-    return true;
-}
-// no completion ring shares its entry array or its consumer word with a ring of the step (the step's own rules are the
-// step's: a ring it will refuse anyway refuses here too)
-bool loop_rings_ok(const xsk_gpu_ring_dev* comp, uint32_t n_comp, const xsk_gpu_ring_dev* rx,
-                   const xsk_gpu_ring_dev* fill, const xsk_gpu_ring_dev* tx, uint32_t n_ports,
-                   const xsk_gpu_ring_dev* stack) {
-    if (!rx || !fill || !tx || n_ports < 1u || n_ports > kEpMaxPorts) return false;
-    for (uint32_t q = 0; q < n_comp; ++q) {
-        if (shares(comp + q, rx) || shares(comp + q, fill) || (stack && shares(comp + q, stack))) return false;
-        for (uint32_t p = 0; p < n_ports; ++p)
-            if (shares(comp + q, tx + p)) return false;
-    }
-    return true;
-}
+// ---- the argument rules (complete_ok, loop_rings_ok, loop_complete_ok: xsk_ring_complete_device.h) ----
 
 // The launches, behind the checks.
 int complete_launch(const xsk_gpu_ring_dev* comp, uint32_t n_rings, const xsk_gpu_pool_dev* pool, uint32_t max,
@@ -197,9 +125,11 @@ int xsk_gpu_rx_loop_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_r
                         struct xsk_gpu_stats* d_port_stats, struct xsk_gpu_rx_pass_result* d_res,
                         const struct xsk_gpu_ring_dev* comp, uint32_t n_comp, uint32_t complete_max, uint32_t* d_moved,
                         uint32_t* d_pushed, void* d_workspace, void* stream) {
-    // the completion call's rules before the step launches anything; the step's own stand in front of its first launch
-    if (n_comp && (!complete_ok(comp, n_comp, pool, complete_max, d_moved, d_pushed) ||
-                   !loop_rings_ok(comp, n_comp, rx, fill, tx, n_ports, stack)))
+    // every rule of the call -- the completion call's, the aliasing with the step's rings and the step's own -- before
+    // the step launches anything; the fused call (xsk_loop_fused.hip) checks through the same function
+    if (!loop_complete_ok(d_umem, umem_size, rx, fill, tx, stack, pool, max_batch, opts, d_table, n_entries, default_port,
+                          n_ports, d_bound, d_port_counts, d_stats, d_port_stats, d_res, comp, n_comp, complete_max,
+                          d_moved, d_pushed, d_workspace))
         return -EINVAL;
     const int rc = xsk_gpu_rx_pass_step_dev(d_umem, umem_size, rx, fill, tx, stack, pool, max_batch, opts, d_table,
                                             n_entries, default_port, n_ports, d_bound, d_actions, d_ports, d_port_counts,

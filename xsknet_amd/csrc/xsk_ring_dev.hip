@@ -21,6 +21,7 @@
 #include "../../include/xsk_gpu.h"
 #include "xsk_hip_util.h"
 #include "xsk_ring_dev.h"
+#include "xsk_ring_dev_device.h"
 
 using namespace xskgpu;
 
@@ -32,95 +33,15 @@ static_assert(sizeof(xsk_gpu_desc) == 16, "one 16-B load and store per descripto
 
 namespace {
 
-// What the kernels take of a struct xsk_gpu_ring_dev / xsk_gpu_pool_dev (read when the call is made).
-struct Ring {
-    uint32_t* prod;
-    uint32_t* cons;
-    void* ring;
-    uint32_t size;
-};
-struct Pool {
-    uint64_t* addr;
-    uint32_t* n_free;
-    uint32_t capacity;
-};
-
-// A word this or a later launch of the call stores: a vector load, never the scalar cache.
-__device__ __forceinline__ uint32_t load_word(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ RdWords load_words(const Ring& r) {
-    RdWords w;
-    w.prod = load_word(r.prod);
-    w.cons = load_word(r.cons);
-    return w;
-}
-
-__device__ __forceinline__ uint4* desc_slot(const Ring& r, uint32_t idx) {
-    return reinterpret_cast<uint4*>(r.ring) + rd_slot(idx, r.size);
-}
-__device__ __forceinline__ uint2* addr_slot(const Ring& r, uint32_t idx) {
-    return reinterpret_cast<uint2*>(r.ring) + rd_slot(idx, r.size);
-}
-
-// The plan is only 4-B aligned: eight word loads / stores.
-__device__ __forceinline__ RdPlan load_plan(const xsk_gpu_rx_plan* d_plan) {
-    RdPlan p;
-    p.received = d_plan->received;
-    p.tx_room = d_plan->tx_room;
-    p.refilled = d_plan->refilled;
-    p.rx_cons = d_plan->rx_cons;
-    p.fq_prod = d_plan->fq_prod;
-    p.pool_n = d_plan->pool_n;
-    p.reserved[0] = p.reserved[1] = 0u;
-    return p;
-}
-__device__ __forceinline__ void store_plan(xsk_gpu_rx_plan* d_plan, const RdPlan& p) {
-    d_plan->received = p.received;
-    d_plan->tx_room = p.tx_room;
-    d_plan->refilled = p.refilled;
-    d_plan->rx_cons = p.rx_cons;
-    d_plan->fq_prod = p.fq_prod;
-    d_plan->pool_n = p.pool_n;
-    d_plan->reserved[0] = 0u;
-    d_plan->reserved[1] = 0u;
-}
+// (Ring, Pool, load_word and the begin stage -- begin_decide, begin_copy, begin_publish, rx_begin_small_body:
+// xsk_ring_dev_device.h)
 
 // ---- begin ----
-__device__ __forceinline__ RdPlan begin_decide(const Ring& rx, const Ring& fill, const Ring& tx, const Pool& pool,
-                                               uint32_t max_batch) {
-    return rd_begin_plan(load_words(rx), rx.size, load_words(fill), fill.size, load_words(tx), tx.size,
-                         load_word(pool.n_free), pool.capacity, max_batch);
-}
-// The lanes first, first + stride, ...: a descriptor is one 16-B load and store, an address one 8-B load and store.
-__device__ __forceinline__ void begin_copy(const Ring& rx, const Ring& fill, const Pool& pool, const RdPlan& p,
-                                           xsk_gpu_desc* descs, uint64_t first, uint64_t stride) {
-    for (uint64_t i = first; i < p.received; i += stride)
-        reinterpret_cast<uint4*>(descs)[i] = *desc_slot(rx, p.rx_cons + (uint32_t)i);
-    for (uint64_t i = first; i < p.refilled; i += stride)
-        *addr_slot(fill, p.fq_prod + (uint32_t)i) = reinterpret_cast<const uint2*>(pool.addr)[rd_pop(p.pool_n, (uint32_t)i)];
-}
-__device__ __forceinline__ void begin_publish(const Ring& fill, const Pool& pool, const RdPlan& p) {
-    if (p.received) {  // (a count word above the capacity ends clamped, whatever was popped)
-        if (p.refilled) *fill.prod = rd_begin_fq_prod(p);
-        *pool.n_free = rd_begin_pool_n(p);
-    }
-}
-
 __global__ __launch_bounds__(kRdSmallThreads) void rx_begin_small_kernel(Ring rx, Ring fill, Ring tx, Pool pool,
                                                                          uint32_t max_batch, xsk_gpu_desc* descs,
                                                                          xsk_gpu_rx_plan* d_plan) {
     __shared__ RdPlan s_plan;
-    if (threadIdx.x == 0) s_plan = begin_decide(rx, fill, tx, pool, max_batch);
-    __syncthreads();
-    const RdPlan p = s_plan;
-    begin_copy(rx, fill, pool, p, descs, threadIdx.x, kRdSmallThreads);
-    __threadfence();  // the entries before the words that cover them
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        store_plan(d_plan, p);
-        begin_publish(fill, pool, p);
-    }
+    rx_begin_small_body(rx, fill, tx, pool, max_batch, descs, d_plan, &s_plan);
 }
 
 __global__ __launch_bounds__(kRdWave) void rx_begin_plan_kernel(Ring rx, Ring fill, Ring tx, Pool pool,
@@ -240,16 +161,7 @@ __global__ __launch_bounds__(kRdWave) void tx_complete_publish_kernel(Ring comp,
 }
 
 // ---- the argument rules ----
-bool ring_ok(const xsk_gpu_ring_dev* r, uintptr_t entry_align) {
-    return r && r->d_producer && r->d_consumer && r->d_ring && !((uintptr_t)r->d_producer & 3u) &&
-           !((uintptr_t)r->d_consumer & 3u) && !((uintptr_t)r->d_ring & (entry_align - 1u)) && rd_size_ok(r->size) &&
-           r->reserved == 0u;
-}
-bool pool_ok(const xsk_gpu_pool_dev* p) {
-    return p && p->d_addr && p->d_n_free && !((uintptr_t)p->d_addr & 7u) && !((uintptr_t)p->d_n_free & 3u) &&
-           p->capacity >= 1u && p->reserved == 0u;
-}
-bool bound_ok(uint32_t n) { return n >= 1u && n <= XSK_GPU_MAX_BATCH; }
+// (a ring, a pool, a bound: xsk_ring_ports_device.h)
 bool begin_ok(const xsk_gpu_ring_dev* rx, const xsk_gpu_ring_dev* fill, const xsk_gpu_ring_dev* tx,
               const xsk_gpu_pool_dev* pool, uint32_t max_batch, const void* d_descs, const void* d_plan) {
     return ring_ok(rx, 16u) && ring_ok(fill, 8u) && ring_ok(tx, 16u) && pool_ok(pool) && bound_ok(max_batch) &&
@@ -261,9 +173,6 @@ bool end_ok(const xsk_gpu_ring_dev* rx, const xsk_gpu_ring_dev* tx, const xsk_gp
            !((uintptr_t)d_plan & 3u) && d_tx && !((uintptr_t)d_tx & 15u) && d_free && !((uintptr_t)d_free & 7u) &&
            d_counts && !((uintptr_t)d_counts & 3u) && !((uintptr_t)d_res & 3u);
 }
-
-Ring ring_of(const xsk_gpu_ring_dev* r) { return Ring{r->d_producer, r->d_consumer, r->d_ring, r->size}; }
-Pool pool_of(const xsk_gpu_pool_dev* p) { return Pool{p->d_addr, p->d_n_free, p->capacity}; }
 
 // The launches, behind the checks.
 int begin_launch(const xsk_gpu_ring_dev* rx, const xsk_gpu_ring_dev* fill, const xsk_gpu_ring_dev* tx,

@@ -26,6 +26,7 @@
 #include "../../include/xsk_gpu.h"
 #include "xsk_hip_util.h"
 #include "xsk_ring_pass.h"
+#include "xsk_ring_pass_device.h"
 #include "xsk_ring_ports_device.h"
 
 using namespace xskgpu;
@@ -40,58 +41,11 @@ static_assert(sizeof(Rings) + 2 * sizeof(Ring) + sizeof(Pool) + 12 * 8 <= 4096, 
 
 namespace {
 
-// The stack ring's producer word and room as a lane reads them at the top of its kernel (the loads are in flight while
-// the workgroup decides); nothing without a stack ring.
-struct StackWords {
-    uint32_t prod, room;
-};
-__device__ __forceinline__ StackWords stack_words(const Ring& stack) {
-    const bool has = stack.ring != nullptr;
-    StackWords w;
-    w.prod = has ? load_word(stack.prod) : 0u;
-    w.room = ps_room(has, w.prod, has ? load_word(stack.cons) : 0u, stack.size);
-    return w;
-}
+// (StackWords, PassPlan, pass_place, pass_publish and the one-workgroup form, rx_pass_end_small_body:
+// xsk_ring_pass_device.h)
 
-// What a launch decides about the stack ring from those words and the two totals.
-struct PassPlan {
-    uint32_t prod;    // the stack ring's producer word as read
-    uint32_t taken;   // s
-    uint32_t full;    // Q - s
-    uint32_t n_rest;  // N - s
-};
-__device__ __forceinline__ PassPlan pass_plan(const StackWords& w, uint32_t n_total, uint32_t q_total) {
-    PassPlan p;
-    p.prod = w.prod;
-    p.taken = ps_taken(q_total, w.room);
-    p.full = q_total - p.taken;
-    p.n_rest = ps_n_rest(n_total, p.taken);
-    return p;
-}
-// The totals the scan left behind the count rows.
-__device__ __forceinline__ PassPlan pass_plan_ws(const StackWords& w, const uint32_t* totals, uint32_t n_max) {
-    const uint32_t n_total = ps_total_rest(totals[kPsRowRest], n_max);
-    return pass_plan(w, n_total, ps_total_pass(totals[kPsRowPass], n_total));
-}
-
-// Frame i, not redirected, with ranks n_i and q_i: onto the stack ring, or into the rest.
-__device__ __forceinline__ void pass_place(const Ring& stack, const PassPlan& p, bool pass, uint32_t n_i, uint32_t q_i,
-                                           const xsk_gpu_desc* descs, uint32_t i, uint64_t* rest) {
-    if (ps_on_stack(pass, q_i, p.taken))
-        *desc_slot(stack, p.prod + q_i) = reinterpret_cast<const uint4*>(descs)[i];
-    else
-        rest[ps_rest_pos(n_i, q_i, p.taken)] = desc_addr(descs, i);
-}
-
-// Behind end_publish(): lane 0 completes *d_res, the workgroup's last lane stores the stack ring's producer word.
-__device__ __forceinline__ void pass_publish(const Ring& stack, const PassPlan& p, xsk_gpu_rx_pass_result* d_res) {
-    if (threadIdx.x == 0 && d_res) {
-        d_res->passed = p.taken;
-        d_res->pass_full = p.full;
-    }
-    if (threadIdx.x == blockDim.x - 1u && p.taken) *stack.prod = p.prod + p.taken;
-}
-
+// (The fused loop kernel runs the same statements as rx_pass_end_small_body(), xsk_ring_pass_device.h; called from here
+// the compiler emitted this kernel's 1009 instructions with two registers exchanged, so the kernel keeps its own text.)
 __global__ __launch_bounds__(kPsSmallThreads) void rx_pass_end_small_kernel(
     Ring rx, Rings tx, uint32_t n_ports, Ring stack, Pool pool, const xsk_gpu_rx_plan* d_plan, const xsk_gpu_desc* descs,
     const uint8_t* actions, const uint32_t* d_off, const xsk_gpu_desc* d_tx, const uint64_t* d_free,
@@ -187,16 +141,8 @@ __global__ __launch_bounds__(kRdWave) void rx_pass_end_publish_kernel(Ring rx, R
     pass_publish(stack, p, d_res);
 }
 
-// ---- the argument rules: those of xsk_gpu_rx_ports_end_dev(), and the stack ring's ----
-// NULL, or a descriptor ring that shares neither its entry array nor its producer word with rx or a port's ring
-bool stack_ok(const xsk_gpu_ring_dev* stack, const xsk_gpu_ring_dev* rx, const xsk_gpu_ring_dev* tx, uint32_t n_ports) {
-    if (!stack) return true;
-    if (!ring_ok(stack, 16u) || stack->d_ring == rx->d_ring || stack->d_producer == rx->d_producer) return false;
-    for (uint32_t p = 0; p < n_ports; ++p)
-        if (stack->d_ring == tx[p].d_ring || stack->d_producer == tx[p].d_producer) return false;
-    return true;
-}
-
+// ---- the argument rules: those of xsk_gpu_rx_ports_end_dev(), and the stack ring's (stack_ok, pass_step_ok:
+// xsk_ring_pass_device.h) ----
 int pass_end_launch(const xsk_gpu_ring_dev* rx, const xsk_gpu_ring_dev* tx, uint32_t n_ports,
                     const xsk_gpu_ring_dev* stack, const xsk_gpu_pool_dev* pool, const xsk_gpu_rx_plan* d_plan,
                     const xsk_gpu_desc* d_descs, const uint8_t* d_actions, const uint32_t* d_off,
@@ -270,14 +216,8 @@ int xsk_gpu_rx_pass_step_dev(void* d_umem, uint64_t umem_size, const struct xsk_
                              uint8_t* d_actions, uint8_t* d_ports, struct xsk_gpu_egress_counts* d_port_counts,
                              struct xsk_gpu_stats* d_stats, struct xsk_gpu_stats* d_port_stats,
                              struct xsk_gpu_rx_pass_result* d_res, void* d_workspace, void* stream) {
-    // the rules of xsk_gpu_rx_step_steer_dev() (the workspace's arrays satisfy the composed calls' by layout), and the
-    // stack ring's
-    if (!d_workspace || ((uintptr_t)d_workspace & 15u) || !d_umem || ((uintptr_t)d_umem & 15u) || (umem_size & 15u) ||
-        (umem_size >> 48) || (opts & ~XSK_GPU_OPT_MASK) || ((uintptr_t)d_stats & 7u) || ((uintptr_t)d_port_stats & 7u) ||
-        ((uintptr_t)d_res & 3u) || ((uintptr_t)d_port_counts & 3u) || !bound_ok(max_batch) || !ports_ok(tx, n_ports) ||
-        !ring_ok(rx, 16u) || !ring_ok(fill, 8u) || !pool_ok(pool) || !stack_ok(stack, rx, tx, n_ports) ||
-        (default_port >= n_ports && default_port != XSK_GPU_STEER_PASS) || n_entries > XSK_GPU_STEER_MAX_ENTRIES ||
-        (n_entries && (!d_table || ((uintptr_t)d_table & 7u))) || ((uintptr_t)d_bound & 7u))
+    if (!pass_step_ok(d_umem, umem_size, rx, fill, tx, stack, pool, max_batch, opts, d_table, n_entries, default_port,
+                      n_ports, d_bound, d_port_counts, d_stats, d_port_stats, d_res, d_workspace))
         return -EINVAL;
     uint8_t* const ws = (uint8_t*)d_workspace;
     const RpLayout l = layout_of(max_batch, n_ports);

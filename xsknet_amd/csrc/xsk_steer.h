@@ -229,6 +229,50 @@ XSK_ST_FN size_t st_workspace_bytes(uint32_t n, uint32_t n_ports) {
     return st_cells(n_ports, cp_nwg(n)) * sizeof(uint32_t);
 }
 
+// ---- the partition in one workgroup (xsk_gpu_rx_fused_loop_dev(), xsk_loop_fused_body.h) ----
+// Up to kSt1Frames frames, a lane per frame, kSt1Waves waves: wave_ranks() fills a kSt1Waves x kStMaxPorts count matrix
+// in LDS, cnt[wave][port].  Port p's total is its column's sum, its first slot the sum of the totals of the ports below
+// it (d_off[p]; d_off[n_ports] is the REDIRECT count), and a frame's slot is its port's first slot, the column's counts
+// of the lower waves and the frame's rank among the lower lanes of its wave.  Batch order holds within a port; no atomic
+// hands out a slot.  Host and device: tests/c/test_loop_fused.cpp replays it lane by lane.
+constexpr uint32_t kSt1Frames = XSK_GPU_LOWLAT_MAX;
+constexpr uint32_t kSt1Waves = kSt1Frames / kStWave;
+
+XSK_ST_FN uint32_t st1_port_total(const uint32_t (*cnt)[kStMaxPorts], uint32_t port) {
+    uint32_t sum = 0;
+    for (uint32_t w = 0; w < kSt1Waves; ++w) sum += cnt[w][port];
+    return sum;
+}
+XSK_ST_FN uint32_t st1_lower_waves(const uint32_t (*cnt)[kStMaxPorts], uint32_t wave, uint32_t port) {
+    uint32_t sum = 0;
+    for (uint32_t w = 0; w < kSt1Waves; ++w) sum += w < wave ? cnt[w][port] : 0u;
+    return sum;
+}
+XSK_ST_FN uint32_t st1_slot(uint32_t port_start, uint32_t lower_waves, uint32_t lower_lanes) {
+    return st_slot(port_start, 0u, lower_waves, lower_lanes);
+}
+
+#ifdef __HIPCC__
+// The wave's frames by port: one ballot per distinct port present (the port of the lowest lane not yet served, read
+// into a scalar with readlane, which is readfirstlane over the lanes still to do).
+// s_cnt[wave][port] gets the wave's count of every port present -- the rest of the row was zeroed by the caller -- and
+// the lane learns how many lower lanes of its wave carry its port.
+__device__ __forceinline__ uint32_t wave_ranks(bool redirect, uint32_t port, uint32_t (*s_cnt)[kStMaxPorts]) {
+    const uint32_t lane = cp_lane(), w = cp_wave();
+    uint32_t rank = 0;
+    unsigned long long todo = __ballot(redirect);
+    while (todo) {  // wave-uniform
+        const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)port, (int)__builtin_ctzll(todo));
+        const unsigned long long m = __ballot(redirect && port == p);
+        if (redirect && port == p) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) s_cnt[w][p] = (uint32_t)__popcll(m);
+        todo &= ~m;
+    }
+    return rank;
+}
+#endif  // __HIPCC__
+
+
 }  // namespace xskgpu
 
 #endif  // XSK_STEER_H

@@ -32,23 +32,7 @@ namespace {
 
 typedef unsigned long long u64;
 
-// The wave's frames by port: one ballot per distinct port present (the port of the lowest lane not yet served, read
-// into a scalar with readlane, which is readfirstlane over the lanes still to do).
-// s_cnt[wave][port] gets the wave's count of every port present -- the rest of the row was zeroed by the caller -- and
-// the lane learns how many lower lanes of its wave carry its port.
-__device__ __forceinline__ uint32_t wave_ranks(bool redirect, uint32_t port, uint32_t (*s_cnt)[kStMaxPorts]) {
-    const uint32_t lane = cp_lane(), w = cp_wave();
-    uint32_t rank = 0;
-    u64 todo = __ballot(redirect);
-    while (todo) {  // wave-uniform
-        const uint32_t p = (uint32_t)__builtin_amdgcn_readlane((int)port, (int)__builtin_ctzll(todo));
-        const u64 m = __ballot(redirect && port == p);
-        if (redirect && port == p) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) s_cnt[w][p] = (uint32_t)__popcll(m);
-        todo &= ~m;
-    }
-    return rank;
-}
+// (wave_ranks: the wave's frames by port, one ballot per distinct port present -- xsk_steer.h)
 
 // ---- stage 1 ----
 __global__ __launch_bounds__(kStFrames) void steer_classify_kernel(
