@@ -1269,6 +1269,101 @@ int xsk_gpu_rx_fused_loop_dev(void* d_umem, uint64_t umem_size, const struct xsk
                               uint32_t n_comp, uint32_t complete_max, uint32_t* d_moved, uint32_t* d_pushed,
                               void* d_workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* The loop body over many RX queues in one launch (build-added).  The         */
+/* reference runs one AF_XDP socket per client, each with its own RX, fill, TX and completion   */
+/* rings and its own frame stack, and a NIC hands a process one such set per RX queue.  The     */
+/* fused call above serves one set with one workgroup on one CU; a caller with Q queues makes Q */
+/* such calls one after another.  xsk_gpu_rx_queues_dev() runs the same loop body for Q         */
+/* independent queues as ONE launch of Q workgroups of 1024 threads, one queue per workgroup.   */
+/* No workgroup waits for another, so queues beyond the number of CUs simply wait for a CU.     */
+/*                                                                                            */
+/* struct xsk_gpu_rx_queue: a host struct, one queue's arguments of xsk_gpu_rx_fused_loop_dev(), */
+/* every field with the meaning it has as that call's parameter of the same name.  `opts` is    */
+/* not a field: it is one value for all queues of a call, since it selects the kernel instance. */
+/*                                                                                            */
+/* The arguments of Q queues do not fit a kernel's argument segment (one queue's fill 3704 B of */
+/* its 4096 B), so they live in device memory, in a block the library lays out:                 */
+/*   xsk_gpu_rx_queues_block_size(n_queues): the block's bytes, 64 + n_queues * stride (a 64-B   */
+/*     header, then one packed record per queue at a stride that is a multiple of 64 B); 0 for   */
+/*     n_queues outside [1, XSK_GPU_RX_MAX_QUEUES].                                              */
+/*   xsk_gpu_rx_queues_prepare(queues, n_queues, opts, h_block): host only, no device call, in   */
+/*     the way of xsk_gpu_steer_table_prepare(): it checks, then writes block_size(n_queues)     */
+/*     bytes of HOST memory at h_block -- the header (a magic word, XSK_GPU_ABI_VERSION,         */
+/*     n_queues, opts, the stride) and every queue's record exactly as the fused call packs its   */
+/*     own kernel arguments, padding zeroed: the same input gives the same bytes.  The ring       */
+/*     structs and pool structs are host memory read during the call.  The caller copies the     */
+/*     block to 64-B aligned device memory once, at set-up, by whatever means; the rings'        */
+/*     addresses do not change for the life of the sockets.                                      */
+/*     -EINVAL, with the block untouched: queues or h_block NULL; n_queues outside [1,            */
+/*     XSK_GPU_RX_MAX_QUEUES]; any queue that breaks any rule of xsk_gpu_rx_fused_loop_dev()      */
+/*     with these opts (every rule of xsk_gpu_rx_loop_dev(), the two bounds of                    */
+/*     XSK_GPU_LOWLAT_MAX, a ring whose d_ring is at or above 2^56); two queues that share a     */
+/*     pointer the kernel writes through, by pointer equality among: the d_ring, d_producer and  */
+/*     d_consumer of every ring given (rx, fill, tx[0 .. n_ports), stack, comp[0 .. n_comp)), a  */
+/*     pool's d_addr and d_n_free, d_workspace, d_actions, d_ports, d_port_counts, d_stats,      */
+/*     d_port_stats, d_res, and with n_comp > 0 d_moved and d_pushed.  -ENOMEM, block untouched:  */
+/*     the host had no memory for that check (it sorts the pointers).                            */
+/*     The caller's duty, not checked: d_table and d_bound are read only and may be shared;       */
+/*     d_umem may be shared -- frames of different queues are different chunks, the ownership    */
+/*     contract above; ranges that overlap without being equal are not found.                    */
+/*   xsk_gpu_rx_queues_dev(d_block, n_queues, opts, stream): one launch of n_queues workgroups.   */
+/*     Workgroup q first reads the header: when the magic, the ABI version, n_queues, opts or the */
+/*     stride differs from the call's, it returns BEFORE ITS FIRST STORE -- a block that does    */
+/*     not match the call is a defined no-op, not a walk through someone else's pointers.         */
+/*     Otherwise it runs the loop body on record q, total for any content of any index or count   */
+/*     word as the fused call is.  A block whose content was not produced by                      */
+/*     xsk_gpu_rx_queues_prepare(), beyond what that header check catches, is undefined.          */
+/* Identity: from the same state the call leaves, for every queue, exactly what                  */
+/* xsk_gpu_rx_fused_loop_dev() leaves when called once per queue in ascending order; the content  */
+/* of the workspaces is the only thing excepted.  (d_stats is accumulated by device atomics:     */
+/* that is why two queues may not share one.)                                                    */
+/* Checked before any device call, -EINVAL: d_block NULL or not 64-B aligned; n_queues outside    */
+/* [1, XSK_GPU_RX_MAX_QUEUES]; opts outside XSK_GPU_OPT_MASK.                                     */
+/*                                                                                            */
+/* Asynchronous on `stream`; the call allocates nothing, copies nothing, synchronises nothing    */
+/* and reads no device memory from the host, so a stream under graph capture may contain it:      */
+/* one kernel node.  Ring protocol order and its limits as above.                                */
+/* Kernel (xsk_rx_queues.hip, xsk_rx_queues_ds.hip): workgroup q checks the header, brings its    */
+/* record into LDS by 16-B loads and calls the fused call's loop body unchanged; the body's LDS   */
+/* and the record are above half of a CU's 160 KiB, so one workgroup runs per CU.                */
+/* Which call to use (measured; 8 ports, 9 completion rings, graph replays):    */
+/* this call from two queues on -- 8 queues of 64 mixed frames at opts 0x17 take 126 us against  */
+/* 785 us for 8 fused calls on one stream, 256 queues 296 us against 25.2 ms; the time is not    */
+/* flat in the queue count (1.1 times one queue's at 8 queues, 1.4 to 2.1 at 64, 2.7 to 5.7 at   */
+/* 256).  For ONE queue the fused call: it needs no block, and reading the arguments from memory */
+/* costs up to 1.1 us (1024 x 64-B frames: 50.1 us against 49.0 us, outside the fused call's own */
+/* spread; at 64 mixed frames the two are within it).                                           */
+/* ------------------------------------------------------------------------------------------ */
+#define XSK_GPU_RX_MAX_QUEUES 1024u
+
+struct xsk_gpu_rx_queue {      /* host memory: one queue's arguments of xsk_gpu_rx_fused_loop_dev() */
+    void* d_umem;
+    uint64_t umem_size;
+    const struct xsk_gpu_ring_dev* rx;
+    const struct xsk_gpu_ring_dev* fill;
+    const struct xsk_gpu_ring_dev* tx;      /* n_ports */
+    const struct xsk_gpu_ring_dev* stack;   /* or NULL */
+    const struct xsk_gpu_pool_dev* pool;
+    const struct xsk_gpu_steer_entry* d_table;
+    const uint64_t* d_bound;
+    uint8_t* d_actions;
+    uint8_t* d_ports;
+    struct xsk_gpu_egress_counts* d_port_counts;
+    struct xsk_gpu_stats* d_stats;
+    struct xsk_gpu_stats* d_port_stats;
+    struct xsk_gpu_rx_pass_result* d_res;
+    const struct xsk_gpu_ring_dev* comp;    /* n_comp */
+    uint32_t* d_moved;
+    uint32_t* d_pushed;
+    void* d_workspace;
+    uint32_t max_batch, n_ports, n_entries, default_port, n_comp, complete_max;   /* 176 bytes */
+};
+
+size_t xsk_gpu_rx_queues_block_size(uint32_t n_queues);
+int xsk_gpu_rx_queues_prepare(const struct xsk_gpu_rx_queue* queues, uint32_t n_queues, uint32_t opts, void* h_block);
+int xsk_gpu_rx_queues_dev(const void* d_block, uint32_t n_queues, uint32_t opts, void* stream);
+
 /* Pipelined RX loop: xsk_gpu_rx_step with up to `depth` batches in flight, so that one queue's steps overlap their
  * PCIe round trips instead of paying one per step.  The object owns up to `depth` contexts of `mode` over one
  * registration of the UMEM and hands batches to them in turn.  A LOWLAT pipe stops adding contexts at the first one

@@ -36,6 +36,7 @@ __all__ = [
     "RxSteerResult", "rx_prepare_ports_dev", "rx_end_ports_dev", "rx_step_steer_dev", "rx_step_steer_dev_workspace_size",
     "RxPassResult", "rx_pass_end_dev", "rx_pass_step_dev", "rx_pass_step_dev_workspace_size",
     "COMPLETE_MAX_RINGS", "tx_complete_rings_dev", "rx_loop_dev", "rx_loop_fused_dev",
+    "RX_MAX_QUEUES", "RxQueue", "rx_queue", "rx_queues_block_size", "rx_queues_prepare", "rx_queues_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -77,6 +78,7 @@ STEER_ENTRY_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("port", 
 STEER_PASS, STEER_MAX_PORTS, STEER_MAX_ENTRIES = 0xFF, 64, 1024  # XSK_GPU_STEER_*
 assert STEER_ENTRY_DTYPE.itemsize == 24
 COMPLETE_MAX_RINGS = STEER_MAX_PORTS + 1  # XSK_GPU_COMPLETE_MAX_RINGS: a completion ring per port, and the stack's
+RX_MAX_QUEUES = 1024  # XSK_GPU_RX_MAX_QUEUES: the queues of one rx_queues_dev call
 
 
 class XskGpuError(RuntimeError):
@@ -151,6 +153,23 @@ class RxPassResult(C.Structure):
 assert C.sizeof(RingDev) == 32 and C.sizeof(PoolDev) == 24 and C.sizeof(RxPlan) == 32 and C.sizeof(RxSteerResult) == 32
 assert C.sizeof(RxPassResult) == 32
 
+
+class RxQueue(C.Structure):
+    """struct xsk_gpu_rx_queue (host memory): one queue's arguments of xsk_gpu_rx_fused_loop_dev, for
+    rx_queues_prepare.  rx_queue() builds one from rx_loop_fused_dev's arguments and keeps what it points to alive."""
+    _fields_ = [("d_umem", C.c_void_p), ("umem_size", C.c_uint64), ("rx", C.POINTER(RingDev)),
+                ("fill", C.POINTER(RingDev)), ("tx", C.POINTER(RingDev)), ("stack", C.POINTER(RingDev)),
+                ("pool", C.POINTER(PoolDev)), ("d_table", C.c_void_p), ("d_bound", C.c_void_p),
+                ("d_actions", C.c_void_p), ("d_ports", C.c_void_p), ("d_port_counts", C.c_void_p),
+                ("d_stats", C.c_void_p), ("d_port_stats", C.c_void_p), ("d_res", C.c_void_p),
+                ("comp", C.POINTER(RingDev)), ("d_moved", C.c_void_p), ("d_pushed", C.c_void_p),
+                ("d_workspace", C.c_void_p), ("max_batch", C.c_uint32), ("n_ports", C.c_uint32),
+                ("n_entries", C.c_uint32), ("default_port", C.c_uint32), ("n_comp", C.c_uint32),
+                ("complete_max", C.c_uint32)]
+
+
+assert C.sizeof(RxQueue) == 176
+
 _lib: Optional[C.CDLL] = None
 
 _P = C.c_void_p
@@ -219,6 +238,9 @@ _SIGS = {
                                    C.POINTER(RingDev), C.POINTER(PoolDev), C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32,
                                    C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.POINTER(RingDev), C.c_uint32, C.c_uint32, _P, _P,
                                    _P, _P], C.c_int),
+    "xsk_gpu_rx_queues_block_size": ([C.c_uint32], C.c_size_t),
+    "xsk_gpu_rx_queues_prepare": ([C.POINTER(RxQueue), C.c_uint32, C.c_uint32, _P], C.c_int),
+    "xsk_gpu_rx_queues_dev": ([_P, C.c_uint32, C.c_uint32, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -637,6 +659,45 @@ def rx_loop_fused_dev(umem, rx: RingDev, fill: RingDev, tx, stack: Optional[Ring
         _ptr(ports), _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res),
         _ring_array(comps) if len(comps) else None, len(comps), complete_max, _ptr(moved), _ptr(pushed),
         _ptr(workspace), _stream_ptr(stream)))
+
+
+def rx_queue(umem, rx: RingDev, fill: RingDev, tx, stack: Optional[RingDev], pool: PoolDev, max_batch: int, table,
+             n_entries: int, default_port: int, comps, complete_max: int, workspace, bound=None, actions=None, ports=None,
+             port_counts=None, stats=None, port_stats=None, res=None, moved=None, pushed=None) -> RxQueue:
+    """One RxQueue from the arguments rx_loop_fused_dev takes (`opts` and `stream` belong to the call over all queues).
+    The ctypes ring and pool structs the struct points to are kept alive on the returned object."""
+    keep = (rx, fill, _ring_array(tx) if len(tx) else None, stack, pool, _ring_array(comps) if len(comps) else None)
+    q = RxQueue(_ptr(umem), umem.numel() * umem.element_size(), C.pointer(rx), C.pointer(fill), keep[2],
+                C.pointer(stack) if stack is not None else None, C.pointer(pool), _ptr(table), _ptr(bound),
+                _ptr(actions), _ptr(ports), _ptr(port_counts), _ptr(stats), _ptr(port_stats), _ptr(res), keep[5],
+                _ptr(moved), _ptr(pushed), _ptr(workspace), max_batch, len(tx), n_entries, default_port, len(comps),
+                complete_max)
+    q._keep = keep
+    return q
+
+
+def rx_queues_block_size(n_queues: int) -> int:
+    """xsk_gpu_rx_queues_block_size: bytes of the argument block of n_queues queues; 0 outside [1, RX_MAX_QUEUES]."""
+    return int(lib().xsk_gpu_rx_queues_block_size(n_queues))
+
+
+def rx_queues_prepare(queues, opts: int = 0) -> np.ndarray:
+    """xsk_gpu_rx_queues_prepare: the argument block of rx_queues_dev for `queues` (a sequence of RxQueue) and `opts`, as
+    a uint8 array in host memory.  Copy it to 64-B aligned device memory once; it holds the rings' addresses, so it
+    stays valid while they do.  Raises XskGpuError where any queue breaks a rule of rx_loop_fused_dev or two queues
+    share a pointer the kernel writes through."""
+    n = len(queues)
+    arr = (RxQueue * n)(*queues) if n else None
+    block = np.zeros(max(rx_queues_block_size(n), 1), np.uint8)
+    _check("xsk_gpu_rx_queues_prepare", lib().xsk_gpu_rx_queues_prepare(arr, n, opts, block.ctypes.data))
+    return block
+
+
+def rx_queues_dev(d_block, n_queues: int, opts: int = 0, stream=None) -> None:
+    """xsk_gpu_rx_queues_dev: rx_loop_fused_dev for n_queues independent queues as one launch of n_queues workgroups.
+    `d_block`: rx_queues_prepare's block for the same n_queues and opts, in device memory (a torch tensor, 64-B
+    aligned); a block prepared for another count or other options makes the call a no-op."""
+    _check("xsk_gpu_rx_queues_dev", lib().xsk_gpu_rx_queues_dev(_ptr(d_block), n_queues, opts, _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,

@@ -78,6 +78,10 @@ XSK_GPU__HIDDEN void xsk_gpu__echo_ds_indirect_launch(const void* args, const ui
  * `args`, a LoopFusedArgs; the launch's outcome is left in hipGetLastError(). */
 XSK_GPU__HIDDEN void xsk_gpu__loop_fused_ds_launch(const void* args, void* stream);
 
+/* xsk_rx_queues_ds.hip: launch the dual-stack instance of xsk_gpu_rx_queues_dev()'s kernel (xsk_rx_queues.hip) over
+ * n_queues workgroups, one per record of the block at d_block; the launch's outcome is left in hipGetLastError(). */
+XSK_GPU__HIDDEN void xsk_gpu__rx_queues_ds_launch(const void* d_block, uint32_t n_queues, uint32_t opts, void* stream);
+
 /* xsk_echo.hip: xsk_gpu_echo_dev_opts for counters in mapped host memory (no device atomics): d_stats
  * must be a slot zeroed for this call (a one-workgroup launch stores the counters without reading it).
  * tile: frames per wave of a small batch (xsk_gpu__small_tile), 0 = ceil(n / 16). */
