@@ -1052,7 +1052,9 @@ int xsk_gpu_rx_step_steer_dev(void* d_umem, uint64_t umem_size, const struct xsk
 /* ring in device memory, in batch order, as many as it has room for.  Whoever consumes that    */
 /* ring (a TAP device, an AF_PACKET socket: the caller's) owns the chunks until their addresses */
 /* come back over a completion ring of its own; xsk_gpu_tx_complete_dev(comp, pool, ...) serves */
-/* that side unchanged.                                                                        */
+/* that side unchanged.  (xsk_gpu_neigh_serve_dev(), "Neighbour responder" below, is a consumer  */
+/* on the device: it answers the ARP requests and neighbour solicitations on the ring and       */
+/* hands the rest on.)                                                                          */
 /*                                                                                            */
 /* `stack`: a descriptor ring (entries struct xsk_gpu_desc, 16-B aligned) or NULL; like the     */
 /* other ring structs host memory, read when the call is made.  Every other parameter has the   */
@@ -1405,6 +1407,146 @@ uint32_t xsk_gpu_rx_pipe_inflight(const xsk_gpu_rx_pipe* p);
 /* Contexts the pipe holds (its depth after init; at most the depth asked for).  0 for NULL. */
 uint32_t xsk_gpu_rx_pipe_depth(const xsk_gpu_rx_pipe* p);
 void xsk_gpu_rx_pipe_fini(xsk_gpu_rx_pipe* p);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Neighbour responder: ARP requests and neighbour solicitations answered on the device.        */
+/* ------------------------------------------------------------------------------------------ */
+/* The first consumer of the stack ring that lives on the device.  Before anybody
+ * sends an echo request to an address of the steering table they send an ARP request (RFC 826) or a
+ * neighbour solicitation (RFC 4861 §7.1.1, §7.2.4) for it; the filter passes both, and
+ * xsk_gpu_rx_pass_step_dev() puts them on the stack ring.  The calls below answer them for the
+ * addresses of a table, rewriting each request into its reply in place, and pass everything else on.
+ *
+ * The table: n_entries <= XSK_GPU_NEIGH_MAX_ENTRIES entries in device memory (8-B aligned), strictly
+ * ascending by the 17 bytes (family, addr) as memcmp orders them; addr, family and port as in
+ * struct xsk_gpu_steer_entry, mac the link-layer address that owns addr (the reply's source).  The
+ * device calls do not check a table: an unprepared one may miss, but no read leaves
+ * d_table[0, n_entries).
+ *
+ * The per-frame rule.  Inputs: one descriptor, the UMEM, opts (a subset of XSK_GPU_OPT_MASK), the
+ * table, n_ports in [1, 64] and the bound word (*d_bound, all ones for NULL).  Output: a verdict of
+ * enum xsk_gpu_neigh_verdict.  Only ARP_REPLY and NA_REPLY change a byte of the frame; only bytes of
+ * [addr, addr + len) are ever read; the first rule that applies decides.  be16(x) is the big-endian
+ * word at frame offset x.
+ *  1. len > XSK_GPU_MAX_LEN, [addr, addr + len) not inside the UMEM, or len < 14: NONE.
+ *  2. l3 and et as rule 3 of the ingress filter with options: tags (0x8100, 0x88A8) are skipped only
+ *     with XSK_GPU_OPT_VLAN, at most two; a tag cut by the frame end: NONE.  opts == 0: l3 = 14.
+ *  3. et == 0x0806, whatever opts:
+ *     a. len < l3 + 28: MALFORMED.
+ *     b. be16(l3) != 1, be16(l3+2) != 0x0800, byte l3+4 != 6 or byte l3+5 != 4: MALFORMED.
+ *     c. be16(l3+6) != 1: NONE (a reply or another operation: whoever keeps a neighbour cache).
+ *     d. key (4, tpa = bytes [l3+24, l3+28)); no entry: UNKNOWN.
+ *     e. the entry's port >= n_ports, or its bound bit clear: UNBOUND.
+ *     f. ARP_REPLY.  With m the entry's mac and sha the old bytes [l3+8, l3+14): bytes [0,6) = sha,
+ *        [6,12) = m, be16(l3+6) = 2, sha = m, spa = old tpa, tha = old sha, tpa = old spa.  Tags,
+ *        ethertype and every byte from l3+28 on are untouched.  The reply length is len.
+ *  4. et == 0x86DD with XSK_GPU_OPT_IPV6:
+ *     a. len < l3 + 40, version nibble != 6, or byte l3+6 != 58: NONE.
+ *     b. len < l3 + 48: MALFORMED.  Byte l3+40 != 135: NONE.
+ *     c. with pl = be16(l3+4) and the target T = bytes [l3+48, l3+64), MALFORMED for: hop limit
+ *        (byte l3+7) != 255; code (byte l3+41) != 0; pl < 24; l3 + 40 + pl > len; T[0] == 0xFF;
+ *        (pl - 24) % 8 != 0.
+ *     d. pl > 280: LEFT (no lane sums past byte l3 + 40 + 280).
+ *     e. the options walk from o = 24: while o < pl, with L = message byte o+1: L == 0 or
+ *        o + 8L > pl: MALFORMED; else o += 8L.
+ *     f. the RFC 1071 sum over the RFC 8200 §8.1 pseudo-header (src, dst, pl, 58) and the message
+ *        bytes [l3+40, l3+40+pl) is not 0xFFFF: MALFORMED (always checked: RFC 4861 requires it).
+ *     g. source address all zero (duplicate address detection): LEFT.  pl < 32 (no room for the
+ *        target link-layer option inside the received length): LEFT.
+ *     h. key (6, T); no entry: UNKNOWN; the port rule of 3e: UNBOUND.
+ *     i. NA_REPLY.  With m the entry's mac and S the old source: bytes [0,6) = old [6,12), [6,12) =
+ *        m; tags and ethertype untouched; bytes l3+0..3 = 60 00 00 00, be16(l3+4) = 32, byte l3+6 =
+ *        58, byte l3+7 = 255, src = T, dst = S; the 32-byte message 88 00 cs cs 60 00 00 00, T,
+ *        02 01, m, with cs the one's complement of the RFC 1071 sum over pseudo(T, S, 32, 58) and
+ *        the message with cs = 0.  The reply length is l3 + 72 (<= len by 4c and 4g); bytes from
+ *        l3 + 72 on are untouched.
+ *  5. Anything else: NONE. */
+#define XSK_GPU_NEIGH_MAX_ENTRIES 1024u
+
+struct xsk_gpu_neigh_entry {   /* 24 bytes */
+    uint8_t addr[16];          /* family 4: four address bytes, then twelve zeros */
+    uint8_t family;            /* 4 or 6 */
+    uint8_t port;              /* < 64 */
+    uint8_t mac[6];            /* the link-layer address that owns addr */
+};
+
+enum xsk_gpu_neigh_verdict {
+    XSK_GPU_NEIGH_NONE = 0,      /* not a request the responder knows */
+    XSK_GPU_NEIGH_ARP_REPLY = 1, /* rewritten into the ARP reply */
+    XSK_GPU_NEIGH_NA_REPLY = 2,  /* rewritten into the neighbour advertisement */
+    XSK_GPU_NEIGH_MALFORMED = 3,
+    XSK_GPU_NEIGH_UNKNOWN = 4,   /* a valid request for an address the table does not hold */
+    XSK_GPU_NEIGH_UNBOUND = 5,   /* the entry's port is not bound */
+    XSK_GPU_NEIGH_LEFT = 6       /* a valid solicitation left to the host's stack */
+};
+
+struct xsk_gpu_neigh_stats {   /* 32 bytes, device memory, 8-B aligned, accumulated */
+    uint64_t seen, arp_replies, na_replies, reply_bytes;
+};
+
+struct xsk_gpu_neigh_result {  /* 32 bytes, device memory, 4-B aligned, written not accumulated */
+    uint32_t consumed;         /* c: entries taken off the stack ring */
+    uint32_t arp_replies;
+    uint32_t na_replies;
+    uint32_t up;               /* entries passed on */
+    uint32_t backlog;          /* used(stack) - c */
+    uint32_t reserved[3];      /* 0 */
+};
+
+/* Host only.  Checks, then sorts in place, as xsk_gpu_steer_table_prepare.  -EINVAL, the array
+ * untouched, for n > XSK_GPU_NEIGH_MAX_ENTRIES, NULL entries with n > 0, a family other than 4 or 6, a
+ * family-4 entry with a nonzero byte in addr[4..16), a port >= 64, a mac that is all zero or has the
+ * group bit set (mac[0] & 1), a family-6 addr that is multicast (addr[0] == 0xFF) or all zero.
+ * -EEXIST for duplicate keys, the array left sorted.  n == 0 returns 0. */
+int xsk_gpu_neigh_table_prepare(struct xsk_gpu_neigh_entry* entries, uint32_t n);
+
+/* The rule over a device-resident list.  n = d_n ? min(*d_n, n_max) : n_max, the word read when the
+ * kernel executes.  For i < n: d_nverdicts[i] the verdict, d_nports[i] the entry's port for the two
+ * replies and 0xFF otherwise, d_reply_len[i] (may be NULL) the reply length for the two replies and
+ * not written otherwise.  Nothing at an index >= n is read or written.  d_nstats (may be NULL) is
+ * accumulated: at most one atomic per workgroup and counter word, none for an addend of 0.  One
+ * launch of 256-thread workgroups sized by n_max, a lane per frame, the table staged into LDS;
+ * n_max == 0 launches nothing.  No workspace.  Asynchronous and graph-capturable.  Two descriptors
+ * over the same bytes are the caller's duty.
+ * -EINVAL before any device call: d_umem, d_descs, d_nverdicts or d_nports NULL; d_descs not 16-B,
+ * d_table, d_bound or d_nstats not 8-B, d_n or d_reply_len not 4-B aligned; opts &
+ * ~XSK_GPU_OPT_MASK; n_ports outside [1, 64]; n_entries > XSK_GPU_NEIGH_MAX_ENTRIES; n_entries > 0
+ * with d_table NULL; n_max > XSK_GPU_MAX_BATCH. */
+int xsk_gpu_neigh_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs,
+                      const uint32_t* d_n, uint32_t n_max, uint32_t opts,
+                      const struct xsk_gpu_neigh_entry* d_table, uint32_t n_entries,
+                      uint32_t n_ports, const uint64_t* d_bound,
+                      uint8_t* d_nverdicts, uint8_t* d_nports, uint32_t* d_reply_len,
+                      struct xsk_gpu_neigh_stats* d_nstats, void* stream);
+
+/* The consumer of the stack ring.  stack is consumed (the descriptor ring xsk_gpu_rx_pass_step_dev
+ * produces); tx[p] are the ports' TX rings, the rings the step serves (the stream orders the two
+ * calls); up is a descriptor ring toward whoever handles the rest, required; max in
+ * [1, XSK_GPU_LOWLAT_MAX].  Total for any content of any index word: used and free are clamped as
+ * everywhere (min((producer - consumer) mod 2^32, size)).  The rule is sequential:
+ *   m = min(used(stack), max); every ring's free count is read at execution;
+ *   for j = 0 .. m-1, with e_j the stack entry at (consumer + j) & mask: decide e_j by the rule above
+ *   (the decision changes nothing); with ARP_REPLY or NA_REPLY the destination is tx[port] and the
+ *   entry to store { e_j.addr, reply length, 0 }, otherwise the destination is up and the entry e_j,
+ *   all 16 bytes; if the destination has no free entry left, counting what this call has already
+ *   given it, stop; otherwise rewrite the frame (the two replies) and store the entry at the
+ *   destination's producer plus the number of earlier entries given to it.
+ * With c the entries handled: *stack.d_consumer += c, every destination's producer advances by what
+ * it received; no store goes to an index word that does not move; entries are stored before the
+ * word that covers them.  A frame behind the stopping point is untouched and stays on the stack
+ * ring.  *d_res (may be NULL) = { c, ARP replies, NAs, entries to up, used(stack) - c, 0, 0, 0 };
+ * d_nstats as above, over the c entries.  One launch of one 1024-thread workgroup; no workspace.
+ * Asynchronous and graph-capturable.
+ * -EINVAL before any device call: the ring rules of xsk_gpu_rx_pass_end_dev for every ring; up
+ * NULL; any two of stack, up, tx[p] sharing d_ring, d_producer or d_consumer; max outside
+ * [1, 1024]; d_umem NULL; d_res not 4-B aligned; the table, option, port and d_bound / d_nstats
+ * rules above. */
+int xsk_gpu_neigh_serve_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_ring_dev* stack,
+                            const struct xsk_gpu_ring_dev* tx /* n_ports */, uint32_t n_ports,
+                            const struct xsk_gpu_ring_dev* up, uint32_t max, uint32_t opts,
+                            const struct xsk_gpu_neigh_entry* d_table, uint32_t n_entries,
+                            const uint64_t* d_bound, struct xsk_gpu_neigh_stats* d_nstats,
+                            struct xsk_gpu_neigh_result* d_res, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Bench / test utilities (not on the hot path).                                               */

@@ -37,6 +37,9 @@ __all__ = [
     "RxPassResult", "rx_pass_end_dev", "rx_pass_step_dev", "rx_pass_step_dev_workspace_size",
     "COMPLETE_MAX_RINGS", "tx_complete_rings_dev", "rx_loop_dev", "rx_loop_fused_dev",
     "RX_MAX_QUEUES", "RxQueue", "rx_queue", "rx_queues_block_size", "rx_queues_prepare", "rx_queues_dev",
+    "NEIGH_ENTRY_DTYPE", "NEIGH_STATS_DTYPE", "NEIGH_RESULT_DTYPE", "NEIGH_MAX_ENTRIES", "NEIGH_VERDICTS",
+    "NEIGH_NONE", "NEIGH_ARP_REPLY", "NEIGH_NA_REPLY", "NEIGH_MALFORMED", "NEIGH_UNKNOWN", "NEIGH_UNBOUND", "NEIGH_LEFT",
+    "neigh_table_prepare", "neigh_dev", "neigh_serve_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -79,6 +82,17 @@ STEER_PASS, STEER_MAX_PORTS, STEER_MAX_ENTRIES = 0xFF, 64, 1024  # XSK_GPU_STEER
 assert STEER_ENTRY_DTYPE.itemsize == 24
 COMPLETE_MAX_RINGS = STEER_MAX_PORTS + 1  # XSK_GPU_COMPLETE_MAX_RINGS: a completion ring per port, and the stack's
 RX_MAX_QUEUES = 1024  # XSK_GPU_RX_MAX_QUEUES: the queues of one rx_queues_dev call
+# struct xsk_gpu_neigh_entry (24 B): one row of the neighbour responder's table, key (family, addr) -> port, mac
+NEIGH_ENTRY_DTYPE = np.dtype([("addr", "u1", (16,)), ("family", "u1"), ("port", "u1"), ("mac", "u1", (6,))])
+# struct xsk_gpu_neigh_stats (32 B, accumulated) and struct xsk_gpu_neigh_result (32 B, written)
+NEIGH_STATS_DTYPE = np.dtype([("seen", "<u8"), ("arp_replies", "<u8"), ("na_replies", "<u8"), ("reply_bytes", "<u8")])
+NEIGH_RESULT_DTYPE = np.dtype([("consumed", "<u4"), ("arp_replies", "<u4"), ("na_replies", "<u4"), ("up", "<u4"),
+                               ("backlog", "<u4"), ("reserved", "<u4", (3,))])
+assert NEIGH_ENTRY_DTYPE.itemsize == 24 and NEIGH_STATS_DTYPE.itemsize == 32 and NEIGH_RESULT_DTYPE.itemsize == 32
+NEIGH_MAX_ENTRIES = 1024  # XSK_GPU_NEIGH_MAX_ENTRIES
+# enum xsk_gpu_neigh_verdict
+NEIGH_NONE, NEIGH_ARP_REPLY, NEIGH_NA_REPLY, NEIGH_MALFORMED, NEIGH_UNKNOWN, NEIGH_UNBOUND, NEIGH_LEFT = range(7)
+NEIGH_VERDICTS = ["NONE", "ARP_REPLY", "NA_REPLY", "MALFORMED", "UNKNOWN", "UNBOUND", "LEFT"]
 
 
 class XskGpuError(RuntimeError):
@@ -241,6 +255,11 @@ _SIGS = {
     "xsk_gpu_rx_queues_block_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_rx_queues_prepare": ([C.POINTER(RxQueue), C.c_uint32, C.c_uint32, _P], C.c_int),
     "xsk_gpu_rx_queues_dev": ([_P, C.c_uint32, C.c_uint32, _P], C.c_int),
+    "xsk_gpu_neigh_table_prepare": ([_P, C.c_uint32], C.c_int),
+    "xsk_gpu_neigh_dev": ([_P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
+                           _P], C.c_int),
+    "xsk_gpu_neigh_serve_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.c_uint32, C.POINTER(RingDev),
+                                 C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -698,6 +717,37 @@ def rx_queues_dev(d_block, n_queues: int, opts: int = 0, stream=None) -> None:
     `d_block`: rx_queues_prepare's block for the same n_queues and opts, in device memory (a torch tensor, 64-B
     aligned); a block prepared for another count or other options makes the call a no-op."""
     _check("xsk_gpu_rx_queues_dev", lib().xsk_gpu_rx_queues_dev(_ptr(d_block), n_queues, opts, _stream_ptr(stream)))
+
+
+def neigh_table_prepare(entries: np.ndarray) -> np.ndarray:
+    """xsk_gpu_neigh_table_prepare on a copy of a host array of NEIGH_ENTRY_DTYPE: checked and sorted by (family, addr),
+    the order the responder's search needs.  Raises XskGpuError (-EINVAL, -EEXIST)."""
+    e = np.array(entries, dtype=NEIGH_ENTRY_DTYPE, copy=True).reshape(-1)
+    _check("xsk_gpu_neigh_table_prepare", lib().xsk_gpu_neigh_table_prepare(e.ctypes.data if len(e) else None, len(e)))
+    return e
+
+
+def neigh_dev(umem, descs, n_max: int, table, n_entries: int, n_ports: int, nverdicts, nports, count=None, bound=None,
+              reply_len=None, nstats=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_neigh_dev: answer the ARP requests and neighbour solicitations among the first min(*count, n_max)
+    descriptors (n_max without `count`, one uint32 word on the device read when the kernel executes) for the addresses of
+    `table` (a device copy of a neigh_table_prepare()d array, or None with n_entries == 0), in place.  nverdicts[i] is
+    the NEIGH_* verdict, nports[i] the owning port of a reply (0xFF otherwise), reply_len[i] (optional) its length;
+    `nstats` (one NEIGH_STATS_DTYPE on the device, optional) is accumulated.  `bound` as in steer_dev."""
+    _check("xsk_gpu_neigh_dev", lib().xsk_gpu_neigh_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), _ptr(count), n_max, opts, _ptr(table), n_entries,
+        n_ports, _ptr(bound), _ptr(nverdicts), _ptr(nports), _ptr(reply_len), _ptr(nstats), _stream_ptr(stream)))
+
+
+def neigh_serve_dev(umem, stack: RingDev, tx, up: RingDev, max_entries: int, table, n_entries: int, bound=None,
+                    nstats=None, res=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_neigh_serve_dev: the consumer of the stack ring rx_pass_step_dev produces.  Up to max_entries
+    (<= LOWLAT_MAX) entries of `stack` are decided by neigh_dev's rule: a reply is written in place and its descriptor
+    goes onto tx[port] (a sequence of RingDev, the ports' TX rings), every other entry onto `up` as it is; the call stops
+    in front of the first entry whose destination is full.  `res`: one NEIGH_RESULT_DTYPE on the device, written."""
+    _check("xsk_gpu_neigh_serve_dev", lib().xsk_gpu_neigh_serve_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), C.byref(stack), _ring_array(tx), len(tx), C.byref(up),
+        max_entries, opts, _ptr(table), n_entries, _ptr(bound), _ptr(nstats), _ptr(res), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,
