@@ -409,6 +409,8 @@ static const uint32_t kSizes[] = {1u, 2u, 8u, 64u, 512u, 4096u};
 enum Mix { kMixed, kAllPass, kNoPass, kAllRedirect };
 enum StackKind { kNoStack, kRoom0, kRoom1, kRoomQm1, kRoomQ, kRoomAbove, kStackKinds };
 static uint64_t g_cases = 0, g_cut = 0, g_conserved = 0, g_tail = 0, g_some = 0, g_all = 0, g_none = 0, g_identity = 0;
+static uint64_t g_bad_back = 0;  // a descriptor that does not fit any UMEM was dropped and its address reached the pool
+static const uint64_t kBadAddr = 0xFFFFFFFFFFFFFFF0ull;
 
 // `frames` received frames steered to n_ports ports and served by the egress's rule; pool_kind 0: full (takes none),
 // 1: room for about half the list, 2: room for all.
@@ -434,6 +436,11 @@ static void steered_case(uint32_t n_ports, uint32_t start, uint32_t frames, uint
             if (mix == kAllPass) a = XSK_GPU_XDP_PASS;
             if (mix == kNoPass && a == XSK_GPU_XDP_PASS) a = XSK_GPU_XDP_DROP;
             if (mix == kAllRedirect) a = XSK_GPU_XDP_REDIRECT;
+            if (mix == kMixed && i == frames / 2u) {  // the row the filter drops unread: an address no UMEM holds
+                in.descs[i].addr = kBadAddr;
+                in.descs[i].len = 64u;
+                a = XSK_GPU_XDP_DROP;
+            }
             in.actions[i] = a;
             Q += a == XSK_GPU_XDP_PASS;
             if (a == XSK_GPU_XDP_REDIRECT) {
@@ -541,6 +548,10 @@ static void steered_case(uint32_t n_ports, uint32_t start, uint32_t frames, uint
         std::sort(want.begin(), want.end());
         CHECK(got == want, "%s: conservation", tag);
         g_conserved++;
+        if (mix == kMixed && frames) {  // the end stage returns the dropped row's address as a number, like any other
+            CHECK(std::count(w.pool.begin(), w.pool.end(), kBadAddr) == 1, "%s: the bad descriptor's address", tag);
+            g_bad_back++;
+        }
     } else {
         g_tail++;
     }
@@ -662,6 +673,7 @@ int main() {
     for (uint32_t np : ports)
         for (uint32_t k = 0; k < 150; ++k)
             garbage_case(np, k % 2u ? 1u + (uint32_t)(rnd64() % 1024u) : 1025u + (uint32_t)(rnd64() % 400u), k);
+    CHECK(g_bad_back > 50, "the bad descriptor's address never reached the pool (%llu)", (unsigned long long)g_bad_back);
     CHECK(g_cut > 50 && g_conserved > 100 && g_tail > 100 && g_none > 50 && g_some > 100 && g_all > 100 && g_identity > 100,
           "the cases never cut (%llu), conserved (%llu), dropped (%llu), took none (%llu), some (%llu), all (%llu) or met the "
           "identity (%llu)",
