@@ -1549,6 +1549,84 @@ int xsk_gpu_neigh_serve_dev(void* d_umem, uint64_t umem_size, const struct xsk_g
                             struct xsk_gpu_neigh_result* d_res, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* The RX loop body and the neighbour responder in one launch (build-added).   */
+/* ------------------------------------------------------------------------------------------ */
+/* Steer + echo + neighbour is a self-standing ping responder with no word to the host; as
+ * xsk_gpu_rx_fused_loop_dev() followed by xsk_gpu_neigh_serve_dev() it is two launches of one
+ * workgroup each.  xsk_gpu_responder_dev() is both in ONE launch: the serve call's body runs in the loop
+ * kernel's own 1024 threads behind a fence and a barrier, on the rings that kernel has already
+ * unpacked.
+ *
+ * struct xsk_gpu_responder_queue (host memory): q holds the fused call's arguments, every field as
+ * there, with q.stack required; up, d_ntable, n_nentries, d_nstats, d_nres and serve_max are the serve
+ * call's up, d_table, n_entries, d_nstats, d_res and max.  There is one option word and one d_bound
+ * (q.d_bound) for both halves.
+ *
+ * Identity: from the same state xsk_gpu_responder_dev(r, opts, s) leaves exactly what these two calls
+ * leave, made in this order on one stream:
+ *   xsk_gpu_rx_fused_loop_dev(the fields of r->q, opts, ..., s);
+ *   xsk_gpu_neigh_serve_dev(q.d_umem, q.umem_size, q.stack, q.tx, q.n_ports, r->up, r->serve_max,
+ *                           opts, r->d_ntable, r->n_nentries, q.d_bound, r->d_nstats, r->d_nres, s);
+ * -- every ring entry and index word (up's and the stack ring's consumer word among them), the pool,
+ * every UMEM byte, every output of the fused call, *d_nres and *d_nstats; only the workspace's content
+ * is excepted.  The serve stage reads every index word after the loop body has published its own, so
+ * a request the step puts on the stack ring in this call is answered in this call, and a reply finds
+ * the room the step's own replies left on its port's TX ring.  Total for any content of any index or
+ * count word, as both halves are.
+ * -EINVAL before any device call: r NULL; any rule of xsk_gpu_rx_fused_loop_dev() or of
+ * xsk_gpu_neigh_serve_dev() (each checked by the function that call checks with); q.stack NULL; up
+ * sharing d_ring, d_producer or d_consumer with any ring given (rx, fill, tx[0 .. n_ports), stack,
+ * comp[0 .. n_comp)).
+ *
+ * Many queues, as xsk_gpu_rx_queues_dev() has them:
+ *   xsk_gpu_responder_block_size(n_queues): 64 + n_queues * stride bytes (the stride a multiple of
+ *     64 B; a record is the one-queue kernel's arguments); 0 outside [1, XSK_GPU_RX_MAX_QUEUES].
+ *   xsk_gpu_responder_prepare(queues, n_queues, opts, h_block): host only, no device call; checks, then
+ *     writes block_size(n_queues) bytes of HOST memory -- a header (a magic word of this call's own,
+ *     XSK_GPU_ABI_VERSION, n_queues, opts, the stride, a record's bytes) and every queue's record,
+ *     padding zeroed: the same input gives the same bytes.  -EINVAL with the block untouched: queues
+ *     or h_block NULL; n_queues out of range; a queue xsk_gpu_responder_dev() would refuse; two queues
+ *     that share a pointer the kernel writes through -- xsk_gpu_rx_queues_prepare()'s list, and up's
+ *     d_ring, d_producer and d_consumer, d_nstats and d_nres.  d_ntable is read only and may be
+ *     shared, as d_table, d_bound and d_umem may.  -ENOMEM, block untouched, as there.
+ *   xsk_gpu_responder_queues_dev(d_block, n_queues, opts, stream): one launch of n_queues workgroups.
+ *     Workgroup q reads the first 24 bytes of the header and returns BEFORE ITS FIRST STORE when the
+ *     magic, the ABI version, n_queues, opts, the stride or the record size differs from the call's:
+ *     a block prepared for another call -- an xsk_gpu_rx_queues_prepare() block among them, and this
+ *     call's block handed to xsk_gpu_rx_queues_dev() -- is a defined no-op.  Otherwise it leaves for
+ *     every queue exactly what xsk_gpu_responder_dev() leaves when called queue after queue in
+ *     ascending order.  -EINVAL before any device call: d_block NULL or not 64-B aligned; n_queues
+ *     out of range; opts outside XSK_GPU_OPT_MASK.
+ * Both device calls are asynchronous on `stream`, allocate nothing, copy nothing, read no device
+ * memory from the host, and are one kernel node each under graph capture.
+ * Kernels (xsk_responder.hip, xsk_responder_ds.hip, xsk_responder_body.h): reference, wire and
+ * dual-stack instances of a one-workgroup kernel and of a workgroup-per-queue kernel; the serve
+ * stage's LDS is one more member of the loop body's overlay, the table staged behind the fence.
+ * Which call to use (measured; 64 frames of which 8 are requests, 8 ports, opts
+ * 0x17): xsk_gpu_responder_queues_dev() for many queues (measured at 8 and 64, not at 2) -- 8
+ * queues take 63 us as a graph replay between device events against 174 us for
+ * xsk_gpu_rx_queues_dev() and 8 serve calls on one stream,
+ * 64 queues 114 us against 1110 us (enqueued: 76 against 356, 130 against 1141).  For ONE queue
+ * xsk_gpu_responder_dev(): it needs no block; enqueued it takes 85 us against 96 us for the two calls
+ * it replaces, but as a graph replay only 59.2 against 60.0 us (69.8 against 71.2 us by the host
+ * clock) -- a caller that has the two calls captured already gains little.  No leg was measured
+ * where the one-launch form is slower. */
+struct xsk_gpu_responder_queue {      /* host memory */
+    struct xsk_gpu_rx_queue q;        /* the fused call's arguments, every field as there; q.stack is required */
+    const struct xsk_gpu_ring_dev* up;            /* required: the serve call's `up` */
+    const struct xsk_gpu_neigh_entry* d_ntable;   /* the neighbour table (NULL iff n_nentries == 0) */
+    struct xsk_gpu_neigh_stats* d_nstats;         /* or NULL, accumulated */
+    struct xsk_gpu_neigh_result* d_nres;          /* or NULL, written */
+    uint32_t n_nentries, serve_max;               /* serve_max in [1, XSK_GPU_LOWLAT_MAX] */
+};
+
+int xsk_gpu_responder_dev(const struct xsk_gpu_responder_queue* r, uint32_t opts, void* stream);
+size_t xsk_gpu_responder_block_size(uint32_t n_queues);
+int xsk_gpu_responder_prepare(const struct xsk_gpu_responder_queue* queues, uint32_t n_queues, uint32_t opts,
+                              void* h_block);
+int xsk_gpu_responder_queues_dev(const void* d_block, uint32_t n_queues, uint32_t opts, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Bench / test utilities (not on the hot path).                                               */
 /* ------------------------------------------------------------------------------------------ */
 

@@ -40,6 +40,8 @@ __all__ = [
     "NEIGH_ENTRY_DTYPE", "NEIGH_STATS_DTYPE", "NEIGH_RESULT_DTYPE", "NEIGH_MAX_ENTRIES", "NEIGH_VERDICTS",
     "NEIGH_NONE", "NEIGH_ARP_REPLY", "NEIGH_NA_REPLY", "NEIGH_MALFORMED", "NEIGH_UNKNOWN", "NEIGH_UNBOUND", "NEIGH_LEFT",
     "neigh_table_prepare", "neigh_dev", "neigh_serve_dev",
+    "ResponderQueue", "responder_queue", "responder_dev", "responder_block_size", "responder_prepare",
+    "responder_queues_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -184,6 +186,16 @@ class RxQueue(C.Structure):
 
 assert C.sizeof(RxQueue) == 176
 
+
+class ResponderQueue(C.Structure):
+    """struct xsk_gpu_responder_queue (host memory): one queue's arguments of xsk_gpu_responder_dev -- the fused call's
+    (q, with q.stack required) and the serve call's up, table, counters, result and bound.  responder_queue() builds one."""
+    _fields_ = [("q", RxQueue), ("up", C.POINTER(RingDev)), ("d_ntable", C.c_void_p), ("d_nstats", C.c_void_p),
+                ("d_nres", C.c_void_p), ("n_nentries", C.c_uint32), ("serve_max", C.c_uint32)]
+
+
+assert C.sizeof(ResponderQueue) == 216
+
 _lib: Optional[C.CDLL] = None
 
 _P = C.c_void_p
@@ -258,6 +270,10 @@ _SIGS = {
     "xsk_gpu_neigh_table_prepare": ([_P, C.c_uint32], C.c_int),
     "xsk_gpu_neigh_dev": ([_P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
                            _P], C.c_int),
+    "xsk_gpu_responder_dev": ([C.POINTER(ResponderQueue), C.c_uint32, _P], C.c_int),
+    "xsk_gpu_responder_block_size": ([C.c_uint32], C.c_size_t),
+    "xsk_gpu_responder_prepare": ([C.POINTER(ResponderQueue), C.c_uint32, C.c_uint32, _P], C.c_int),
+    "xsk_gpu_responder_queues_dev": ([_P, C.c_uint32, C.c_uint32, _P], C.c_int),
     "xsk_gpu_neigh_serve_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.c_uint32, C.POINTER(RingDev),
                                  C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
@@ -748,6 +764,49 @@ def neigh_serve_dev(umem, stack: RingDev, tx, up: RingDev, max_entries: int, tab
     _check("xsk_gpu_neigh_serve_dev", lib().xsk_gpu_neigh_serve_dev(
         _ptr(umem), umem.numel() * umem.element_size(), C.byref(stack), _ring_array(tx), len(tx), C.byref(up),
         max_entries, opts, _ptr(table), n_entries, _ptr(bound), _ptr(nstats), _ptr(res), _stream_ptr(stream)))
+
+
+def responder_queue(q: RxQueue, up: RingDev, serve_max: int, ntable, n_nentries: int, nstats=None,
+                    nres=None) -> ResponderQueue:
+    """One ResponderQueue: `q` is rx_queue()'s struct (its stack ring is required), the rest are neigh_serve_dev's up,
+    max_entries, table, n_entries, nstats and res.  The bound word and the options are q's and the call's: one of each
+    for both halves.  What the struct points to is kept alive on the returned object."""
+    r = ResponderQueue(q, C.pointer(up) if up is not None else None, _ptr(ntable), _ptr(nstats), _ptr(nres), n_nentries,
+                       serve_max)
+    r._keep = (q, getattr(q, "_keep", None), up)
+    return r
+
+
+def responder_dev(r: ResponderQueue, opts: int = 0, stream=None) -> None:
+    """xsk_gpu_responder_dev: rx_loop_fused_dev over r.q followed by neigh_serve_dev over its stack ring, as ONE launch of
+    one workgroup; it leaves exactly what those two calls leave.  A request the step puts on the stack ring in this
+    call is answered in this call."""
+    _check("xsk_gpu_responder_dev", lib().xsk_gpu_responder_dev(C.byref(r) if r is not None else None, opts,
+                                                                _stream_ptr(stream)))
+
+
+def responder_block_size(n_queues: int) -> int:
+    """xsk_gpu_responder_block_size: bytes of the argument block of n_queues queues; 0 outside [1, RX_MAX_QUEUES]."""
+    return int(lib().xsk_gpu_responder_block_size(n_queues))
+
+
+def responder_prepare(queues, opts: int = 0) -> np.ndarray:
+    """xsk_gpu_responder_prepare: the argument block of responder_queues_dev for `queues` (a sequence of ResponderQueue)
+    and `opts`, as a uint8 array in host memory; copy it to 64-B aligned device memory once.  Raises XskGpuError where a
+    queue breaks a rule of responder_dev or two queues share a pointer the kernel writes through."""
+    n = len(queues)
+    arr = (ResponderQueue * n)(*queues) if n else None
+    block = np.zeros(max(responder_block_size(n), 1), np.uint8)
+    _check("xsk_gpu_responder_prepare", lib().xsk_gpu_responder_prepare(arr, n, opts, block.ctypes.data))
+    return block
+
+
+def responder_queues_dev(d_block, n_queues: int, opts: int = 0, stream=None) -> None:
+    """xsk_gpu_responder_queues_dev: responder_dev for n_queues independent queues as one launch of n_queues workgroups.
+    `d_block`: responder_prepare's block for the same n_queues and opts, in device memory (64-B aligned); any other
+    block -- another count, other options, an rx_queues_prepare block -- makes the call a no-op."""
+    _check("xsk_gpu_responder_queues_dev",
+           lib().xsk_gpu_responder_queues_dev(_ptr(d_block), n_queues, opts, _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,

@@ -82,6 +82,28 @@ XSK_GPU__HIDDEN void xsk_gpu__loop_fused_ds_launch(const void* args, void* strea
  * n_queues workgroups, one per record of the block at d_block; the launch's outcome is left in hipGetLastError(). */
 XSK_GPU__HIDDEN void xsk_gpu__rx_queues_ds_launch(const void* d_block, uint32_t n_queues, uint32_t opts, void* stream);
 
+/* xsk_rx_queues.hip, for xsk_gpu_responder_dev() and xsk_gpu_responder_prepare() (xsk_responder.hip): one queue against
+ * every rule of xsk_gpu_rx_fused_loop_dev() (1 = accepted); its record, a LoopFusedArgs at `args` whose bytes arrive
+ * zeroed; and the pointers the kernel writes through for it, xsk_gpu_rx_queues_prepare()'s list, into out[0 .. return
+ * value), at most XSK_GPU__RXQ_OWNED_MAX of them (the queue has passed xsk_gpu__rxq_ok; may throw std::bad_alloc). */
+#define XSK_GPU__RXQ_OWNED_MAX 416u /* 3 words of 3 + 64 + 65 rings, 2 of the pool, 9 outputs */
+XSK_GPU__HIDDEN int xsk_gpu__rxq_ok(const struct xsk_gpu_rx_queue* q, uint32_t opts);
+XSK_GPU__HIDDEN void xsk_gpu__rxq_pack(const struct xsk_gpu_rx_queue* q, uint32_t opts, void* args);
+XSK_GPU__HIDDEN uint32_t xsk_gpu__rxq_owned(const struct xsk_gpu_rx_queue* q, const void** out);
+/* xsk_neigh.hip, for the same: every rule of xsk_gpu_neigh_serve_dev() (1 = accepted). */
+XSK_GPU__HIDDEN int xsk_gpu__serve_ok(const void* d_umem, const struct xsk_gpu_ring_dev* stack,
+                                      const struct xsk_gpu_ring_dev* tx, uint32_t n_ports,
+                                      const struct xsk_gpu_ring_dev* up, uint32_t max, uint32_t opts,
+                                      const struct xsk_gpu_neigh_entry* d_table, uint32_t n_entries,
+                                      const uint64_t* d_bound, const struct xsk_gpu_neigh_stats* d_nstats,
+                                      const struct xsk_gpu_neigh_result* d_res);
+/* xsk_responder_ds.hip: launch the dual-stack instances of the responder kernels (xsk_responder.hip): the one-workgroup
+ * kernel with `args`, a ResponderArgs, and the workgroup-per-queue kernel over the block at d_block; the launch's
+ * outcome is left in hipGetLastError(). */
+XSK_GPU__HIDDEN void xsk_gpu__responder_ds_launch(const void* args, void* stream);
+XSK_GPU__HIDDEN void xsk_gpu__responder_queues_ds_launch(const void* d_block, uint32_t n_queues, uint32_t opts,
+                                                         void* stream);
+
 /* xsk_echo.hip: xsk_gpu_echo_dev_opts for counters in mapped host memory (no device atomics): d_stats
  * must be a slot zeroed for this call (a one-workgroup launch stores the counters without reading it).
  * tile: frames per wave of a small batch (xsk_gpu__small_tile), 0 = ceil(n / 16). */

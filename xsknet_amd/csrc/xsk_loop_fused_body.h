@@ -20,6 +20,7 @@
 
 #include "xsk_echo_device.h"
 #include "xsk_egress_ports_device.h"
+#include "xsk_neigh_device.h"
 #include "xsk_ring_complete_device.h"
 #include "xsk_ring_dev_device.h"
 #include "xsk_ring_pack.h"
@@ -96,7 +97,9 @@ union LoopStageLds {
     EgressLds egress;
     EndStageLds end;
     CompLds comp;
+    NgServeLds serve;  // the responder's stage behind the loop body (xsk_responder_body.h); smaller than echo
 };
+static_assert(sizeof(NgServeLds) <= sizeof(Echo6Smem<1>), "the serve stage adds nothing to the overlay");
 // Where the stages' arrays are: the workspace's, or the caller's where the caller gave one.  In LDS, so that no stage
 // holds them in scalar registers across the transform's body.
 struct LoopPtrs {

@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "../../include/xsk_gpu.h"
+#include "xsk_gpu_internal.h"
 #include "xsk_hip_util.h"
 #include "xsk_neigh.h"
 #include "xsk_ring_dev.h"
@@ -128,6 +129,11 @@ __device__ __forceinline__ Ring ring_dev(const PackedRing& p) {
     return Ring{(uint32_t*)u.prod, (uint32_t*)u.cons, (void*)u.ring, u.size};
 }
 
+// The body below is also ng_serve_body(), xsk_neigh_device.h, which the responder kernels call (xsk_responder_body.h).
+// Called from here, with the LDS objects handed in, the compiler emitted the same 2084 instructions in another order
+// (operands of additions commuted, address computations scheduled ahead of the values stored there:
+// profiles/responder/README.md), so this kernel keeps its own text, as egress_ports_small_kernel does, and
+// tests/test_responder_spec.py holds the two texts against each other.
 __global__ __launch_bounds__(kNgServeThreads) void neigh_serve_kernel(ServeArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
     __shared__ Ring s_ring[kNgRings];
@@ -310,6 +316,14 @@ int serve_launch(const ServeArgs& a, hipStream_t s) {
 }
 
 }  // namespace
+
+// For xsk_responder.hip (xsk_gpu_internal.h): the serve call's rules, stated once, here.
+extern "C" int xsk_gpu__serve_ok(const void* d_umem, const struct xsk_gpu_ring_dev* stack, const struct xsk_gpu_ring_dev* tx,
+                                 uint32_t n_ports, const struct xsk_gpu_ring_dev* up, uint32_t max, uint32_t opts,
+                                 const struct xsk_gpu_neigh_entry* d_table, uint32_t n_entries, const uint64_t* d_bound,
+                                 const struct xsk_gpu_neigh_stats* d_nstats, const struct xsk_gpu_neigh_result* d_res) {
+    return serve_ok(d_umem, stack, tx, n_ports, up, max, opts, d_table, n_entries, d_bound, d_nstats, d_res) ? 1 : 0;
+}
 
 extern "C" {
 

@@ -74,29 +74,29 @@ void own_ring(std::vector<Owned>& v, const xsk_gpu_ring_dev* r, uint32_t q) {
 }
 // Every queue has passed queue_ok().  Sorted by pointer, then by queue: two queues that hold the same pointer stand
 // next to each other (what one queue may hold twice is that queue's own rules' business).
+void queue_owned(std::vector<Owned>& v, const xsk_gpu_rx_queue& q, uint32_t k) {
+    own_ring(v, q.rx, k);
+    own_ring(v, q.fill, k);
+    if (q.stack) own_ring(v, q.stack, k);
+    for (uint32_t p = 0; p < q.n_ports; ++p) own_ring(v, q.tx + p, k);
+    for (uint32_t c = 0; c < q.n_comp; ++c) own_ring(v, q.comp + c, k);
+    own(v, q.pool->d_addr, k);
+    own(v, q.pool->d_n_free, k);
+    own(v, q.d_workspace, k);
+    own(v, q.d_actions, k);
+    own(v, q.d_ports, k);
+    own(v, q.d_port_counts, k);
+    own(v, q.d_stats, k);
+    own(v, q.d_port_stats, k);
+    own(v, q.d_res, k);
+    if (q.n_comp) {  // (ignored without completion rings, as the fused call ignores them)
+        own(v, q.d_moved, k);
+        own(v, q.d_pushed, k);
+    }
+}
 bool queues_disjoint(const xsk_gpu_rx_queue* queues, uint32_t n_queues) {
     std::vector<Owned> v;
-    for (uint32_t k = 0; k < n_queues; ++k) {
-        const xsk_gpu_rx_queue& q = queues[k];
-        own_ring(v, q.rx, k);
-        own_ring(v, q.fill, k);
-        if (q.stack) own_ring(v, q.stack, k);
-        for (uint32_t p = 0; p < q.n_ports; ++p) own_ring(v, q.tx + p, k);
-        for (uint32_t c = 0; c < q.n_comp; ++c) own_ring(v, q.comp + c, k);
-        own(v, q.pool->d_addr, k);
-        own(v, q.pool->d_n_free, k);
-        own(v, q.d_workspace, k);
-        own(v, q.d_actions, k);
-        own(v, q.d_ports, k);
-        own(v, q.d_port_counts, k);
-        own(v, q.d_stats, k);
-        own(v, q.d_port_stats, k);
-        own(v, q.d_res, k);
-        if (q.n_comp) {  // (ignored without completion rings, as the fused call ignores them)
-            own(v, q.d_moved, k);
-            own(v, q.d_pushed, k);
-        }
-    }
+    for (uint32_t k = 0; k < n_queues; ++k) queue_owned(v, queues[k], k);
     std::sort(v.begin(), v.end());
     for (size_t i = 1; i < v.size(); ++i)
         if (v[i].first == v[i - 1].first && v[i].second != v[i - 1].second) return false;
@@ -152,6 +152,18 @@ int queues_launch(const uint8_t* d_block, uint32_t n_queues, uint32_t opts, hipS
 }
 
 }  // namespace
+
+// For xsk_responder.hip (xsk_gpu_internal.h): one queue's rules, its record and what it owns, each stated once, here.
+extern "C" int xsk_gpu__rxq_ok(const struct xsk_gpu_rx_queue* q, uint32_t opts) { return queue_ok(*q, opts) ? 1 : 0; }
+extern "C" void xsk_gpu__rxq_pack(const struct xsk_gpu_rx_queue* q, uint32_t opts, void* args) {
+    pack_queue(*q, opts, *(LoopFusedArgs*)args);
+}
+extern "C" uint32_t xsk_gpu__rxq_owned(const struct xsk_gpu_rx_queue* q, const void** out) {
+    std::vector<Owned> v;
+    queue_owned(v, *q, 0u);
+    for (size_t i = 0; i < v.size(); ++i) out[i] = (const void*)v[i].first;
+    return (uint32_t)v.size();
+}
 
 extern "C" {
 
