@@ -7,6 +7,7 @@
 #include "xsk_echo_kernels.h"
 #include "xsk_gpu_internal.h"
 #include "xsk_hip_util.h"
+#include "xsk_rearm_device.h"
 
 using namespace xskgpu;
 
@@ -173,61 +174,6 @@ __global__ __launch_bounds__(256) void stage_gather_kernel(const uint8_t* src, c
     }
 }
 
-// csum_replace2(csum, 0, 8) on the LE-loaded field: the inverse of the transform's (8 -> 0) patch
-__device__ __forceinline__ uint32_t rearm_csum(uint32_t c) {
-    uint32_t x = (~c) & 0xFFFFu;
-    x = (x + 0xFFFFu) & 0xFFFFu;
-    x += x < 0xFFFFu ? 1u : 0u;
-    x = (x + 8u) & 0xFFFFu;
-    x += x < 8u ? 1u : 0u;
-    return (~x) & 0xFFFFu;
-}
-
-// Re-arm TX_REPLY frames (lane per frame; bench utility, not the hot path).  A 16-B aligned frame (every
-// frame the bench generates) is re-armed as its whole 64-B sector -- four 16-B loads, the swaps as dword
-// shuffles, four 16-B stores: no partial-sector writes (the frame owns [addr, addr + max(len, 64)),
-// include/xsk_gpu.h); any other frame byte by byte.
-__global__ __launch_bounds__(256) void rearm_kernel(uint8_t* umem, const xsk_gpu_desc* descs, const uint8_t* verdicts,
-                                                    uint32_t n) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n || verdicts[i] != XSK_GPU_TX_REPLY) return;
-    uint8_t* p = umem + descs[i].addr;
-    if ((descs[i].addr & 15u) == 0) {
-        u32x4* q = (u32x4*)p;
-        u32x4 a = q[0], b = q[1], c = q[2];
-        const u32x4 d = q[3];
-        // bytes 0-11: MACs swapped back (the same shuffle as the transform's, xsk_receive.c:148-151)
-        const uint32_t n0 = (a.y >> 16) | (a.z << 16), n1 = (a.z >> 16) | (a.x << 16), n2 = (a.x >> 16) | (a.y << 16);
-        a.x = n0;
-        a.y = n1;
-        a.z = n2;
-        // dwords 6, 7, 8 = bytes 24-35: IPv4 addresses swapped back (:153-155), type 0 -> 8 (byte 34)
-        const uint32_t h6 = b.z, h7 = b.w, h8 = c.x;
-        b.z = (h6 & 0xFFFFu) | (h7 & 0xFFFF0000u);
-        b.w = (h8 & 0xFFFFu) | (h6 & 0xFFFF0000u);
-        c.x = (h7 & 0xFFFFu) | (h8 & 0xFF000000u) | (8u << 16);
-        c.y = (c.y & 0xFFFF0000u) | rearm_csum(c.y & 0xFFFFu);  // bytes 36-37
-        q[0] = a;
-        q[1] = b;
-        q[2] = c;
-        q[3] = d;
-        return;
-    }
-    uint8_t t[6];
-    for (int k = 0; k < 6; ++k) t[k] = p[k];
-    for (int k = 0; k < 6; ++k) p[k] = p[6 + k];
-    for (int k = 0; k < 6; ++k) p[6 + k] = t[k];
-    for (int k = 0; k < 4; ++k) {
-        const uint8_t x = p[26 + k];
-        p[26 + k] = p[30 + k];
-        p[30 + k] = x;
-    }
-    p[34] = 8;
-    const uint32_t x = rearm_csum((uint32_t)p[36] | ((uint32_t)p[37] << 8));
-    p[36] = (uint8_t)x;
-    p[37] = (uint8_t)(x >> 8);
-}
-
 // Read-only streaming ceiling: every byte loaded once with 16-B nontemporal loads, in the pattern that measured
 // fastest for a plain read (profiles/r01/read_order_ceilings_*.log: 6.8 TB/s on 1.5 GB): one 16-wave workgroup per
 // CU over a contiguous share, each step four 1-KiB wave-loads per wave (64 KiB per workgroup) in flight.
@@ -300,9 +246,14 @@ int xsk_gpu_rearm_dev(void* d_umem, const struct xsk_gpu_desc* d_descs, const ui
     if (n == 0) return 0;
     if (n > XSK_GPU_MAX_BATCH) return -EINVAL;
     if (!d_umem || !d_descs || !d_verdicts) return -EINVAL;
-    hipLaunchKernelGGL(rearm_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (uint8_t*)d_umem, d_descs,
-                       d_verdicts, n);
-    HIP_TRY(hipGetLastError());
+    // re-arm is a bench utility, not the hot path (inside the timed step of bench.py's c5 only)
+    for (uint32_t c = 0; c < rearm_launches(n); ++c) {
+        const uint64_t c0 = (uint64_t)c * kRearmChunk;
+        const uint32_t m = rearm_launch_frames(n, c);
+        hipLaunchKernelGGL(rearm_quads_kernel, dim3((m + kRearmBlockFrames - 1) / kRearmBlockFrames), dim3(kRearmBlock), 0,
+                           (hipStream_t)stream, (uint8_t*)d_umem, d_descs + c0, d_verdicts + c0, m);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 
