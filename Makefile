@@ -19,14 +19,14 @@ all: $(LIB) $(TUNELIB) oracle tools/echo_replay tools/rxqueues tools/rxring
 HDRS     := $(CSRC)/xsk_echo_device.h $(CSRC)/xsk_echo_geometry.h $(CSRC)/xsk_echo_kernels.h $(CSRC)/xsk_hip_util.h $(CSRC)/xsk_gpu_internal.h $(CSRC)/xsk_stage_plan.h \
             $(CSRC)/xsk_lowlat_proto.h $(CSRC)/xsk_ring.h $(CSRC)/xsk_classify_wire.h $(CSRC)/xsk_echo_indirect.h $(CSRC)/xsk_compact.h $(CSRC)/xsk_egress.h $(CSRC)/xsk_egress_ports.h $(CSRC)/xsk_steer.h $(CSRC)/xsk_ring_dev.h $(CSRC)/xsk_ring_ports.h $(CSRC)/xsk_ring_ports_device.h $(CSRC)/xsk_ring_pass.h $(CSRC)/xsk_ring_complete.h \
             $(CSRC)/xsk_ring_dev_device.h $(CSRC)/xsk_egress_ports_device.h $(CSRC)/xsk_ring_pass_device.h $(CSRC)/xsk_ring_complete_device.h $(CSRC)/xsk_ring_pack.h $(CSRC)/xsk_loop_fused_body.h $(CSRC)/xsk_rx_queues.h $(CSRC)/xsk_neigh.h $(CSRC)/xsk_neigh_device.h \
-            $(CSRC)/xsk_responder_body.h $(CSRC)/xsk_responder_block.h $(CSRC)/xsk_rearm_device.h include/xsk_gpu.h
+            $(CSRC)/xsk_responder_body.h $(CSRC)/xsk_responder_block.h $(CSRC)/xsk_rearm_device.h $(CSRC)/xsk_unreach.h $(CSRC)/xsk_unreach_device.h include/xsk_gpu.h
 # build id of the transform kernel: a hash of the sources that define it and of the flags, reported by
 # xsk_gpu_build_id() so bench.py attaches a PMC traffic summary only to the build it was measured on
 # (the device code and its launch: not include/xsk_gpu.h, whose comments change more often than its structs)
 BUILD_ID := $(shell cat $(CSRC)/xsk_echo.hip $(CSRC)/xsk_echo_ds.hip $(CSRC)/xsk_echo_device.h $(CSRC)/xsk_echo_geometry.h $(CSRC)/xsk_echo_kernels.h $(CSRC)/xsk_hip_util.h | sha256sum | cut -c1-16)-$(shell echo '$(HIPFLAGS)' | sha256sum | cut -c1-4)
 HIPOBJ   := $(CSRC)/xsk_echo.o $(CSRC)/xsk_echo_ds.o $(CSRC)/xsk_aux.o $(CSRC)/xsk_classify.o $(CSRC)/xsk_lowlat.o \
             $(CSRC)/xsk_echo_indirect.o $(CSRC)/xsk_echo_ds_indirect.o $(CSRC)/xsk_egress.o $(CSRC)/xsk_steer.o $(CSRC)/xsk_egress_ports.o $(CSRC)/xsk_ring_dev.o $(CSRC)/xsk_ring_ports.o $(CSRC)/xsk_ring_pass.o $(CSRC)/xsk_ring_complete.o \
-            $(CSRC)/xsk_loop_fused.o $(CSRC)/xsk_loop_fused_ds.o $(CSRC)/xsk_rx_queues.o $(CSRC)/xsk_rx_queues_ds.o $(CSRC)/xsk_neigh.o $(CSRC)/xsk_responder.o $(CSRC)/xsk_responder_ds.o
+            $(CSRC)/xsk_loop_fused.o $(CSRC)/xsk_loop_fused_ds.o $(CSRC)/xsk_rx_queues.o $(CSRC)/xsk_rx_queues_ds.o $(CSRC)/xsk_neigh.o $(CSRC)/xsk_responder.o $(CSRC)/xsk_responder_ds.o $(CSRC)/xsk_unreach.o
 HOSTOBJ  := $(CSRC)/xsk_gpu_host.o $(CSRC)/xsk_gpu_mem.o $(CSRC)/xsk_gpu_rx.o $(CSRC)/xsk_gpu_multi.o $(CSRC)/xsk_gpu_pipe.o $(CSRC)/xsk_gpu_umem.o
 TUNEOBJ  := $(CSRC)/tune/xsk_tune_product.o
 

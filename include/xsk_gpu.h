@@ -1627,6 +1627,118 @@ int xsk_gpu_responder_prepare(const struct xsk_gpu_responder_queue* queues, uint
 int xsk_gpu_responder_queues_dev(const void* d_block, uint32_t n_queues, uint32_t opts, void* stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Port-unreachable responder: UDP probes for a closed port answered on the device.             */
+/* ------------------------------------------------------------------------------------------ */
+/* The second consumer in the chain: what xsk_gpu_neigh_serve_dev() passes on to its
+ * `up` ring holds, among the rest, UDP datagrams for our addresses on ports nobody listens on.  A host
+ * answers those with ICMP destination unreachable / port unreachable (RFC 792, RFC 1122 §3.2.2.1) or
+ * ICMPv6 type 1 code 4 (RFC 4443 §3.1): that is how traceroute to the host ends.  The calls below
+ * write that error over the request, in place.  The reply quotes the request behind a fresh header,
+ * so it is LONGER than what it quotes: the frame grows inside its chunk.
+ *
+ * An address is ours when the neighbour table holds it: struct xsk_gpu_neigh_entry and
+ * xsk_gpu_neigh_table_prepare(), unchanged; the entry gives the port and the mac the reply leaves from.
+ *
+ * The per-frame rule.  Inputs: one descriptor, the UMEM, opts (a subset of XSK_GPU_OPT_MASK), the
+ * table, n_ports in [1, 64], the bound word (*d_bound, all ones for NULL), chunk_size (a power of two
+ * in [2048, 2^20]) and d_open (may be NULL): 8192 bytes of device memory, 4-B aligned, bit p & 7 of
+ * byte p >> 3 set when somebody listens on UDP port p; NULL: every port is closed.  Output: a verdict
+ * of enum xsk_gpu_unreach_verdict.  Only UNREACH4 and UNREACH6 change a byte; only bytes of
+ * [addr, addr + len) are read before a reply is decided; the first rule that applies decides.
+ *  1. len > XSK_GPU_MAX_LEN, [addr, addr + len) not inside the UMEM, or len < 14: NONE.
+ *  2. l3 and et as rule 2 of the neighbour responder.
+ *  3. et == 0x0800, whatever opts, with ihl the low nibble of byte l3:
+ *     a. NONE for: len < l3 + 20; high nibble of byte l3 != 4; ihl < 5; len < l3 + 4 ihl; byte l3+9
+ *        != 17.
+ *     b. with tl = be16(l3+2), MALFORMED for: tl < 4 ihl + 8; l3 + tl > len; the RFC 1071 sum of
+ *        [l3, l3 + 4 ihl) is not 0xFFFF (always verified: RFC 1122 §3.2.1.2).
+ *     c. LEFT for: be16(l3+6) & 0x1FFF != 0 (not the first fragment); the group bit in byte 0; the
+ *        destination D = [l3+16, l3+20) with D[0] >= 224; the source S = [l3+12, l3+16) all zero,
+ *        S[0] >= 224 or S[0] == 127 (RFC 1122 §3.2.2).
+ *     d. key (4, D); no entry: UNKNOWN; the port rule of the neighbour responder's 3e: UNBOUND.
+ *     e. d_open given and the bit of be16(l3 + 4 ihl + 2) set: LEFT.
+ *     f. q = 4 ihl + 8, R = l3 + 28 + q; (addr & (chunk_size - 1)) + R > chunk_size, or
+ *        [addr, addr + R) not inside the UMEM: NO_ROOM.
+ *     g. UNREACH4.  With m the entry's mac, every read in front of every write (the ranges
+ *        overlap): bytes [0,6) = old [6,12), [6,12) = m; tags and ethertype untouched;
+ *        [l3+28, l3+28+q) = old [l3, l3+q); at l3: 45 00, be16 = 28 + q, 00 00, 40 00, 40, 01, the
+ *        header checksum, src = D, dst = S; at l3+20: 03 03 cs cs 00 00 00 00, cs the one's
+ *        complement of the sum over [l3+20, l3+28+q) with cs zero.  The reply length is R, smaller
+ *        or larger than len; bytes from addr + R on are untouched.
+ *  4. et == 0x86DD with XSK_GPU_OPT_IPV6:
+ *     a. NONE for: len < l3 + 40; version nibble != 6; byte l3+6 != 17 (no extension headers).
+ *     b. with pl = be16(l3+4), MALFORMED for: pl < 8; l3 + 40 + pl > len; be16(l3+46) == 0 (RFC
+ *        8200 §8.1).
+ *     c. LEFT for: the group bit in byte 0; D[0] == 0xFF; S all zero; S[0] == 0xFF.
+ *     d. key (6, D), UNKNOWN and UNBOUND as in 3d; an open port be16(l3+42): LEFT.
+ *     e. q = min(40 + pl, 1232) (the reply packet is at most the minimum MTU: RFC 4443 §2.4(c)),
+ *        R = l3 + 48 + q; NO_ROOM as in 3f.
+ *     f. UNREACH6.  Macs as in 3g; [l3+48, l3+48+q) = old [l3, l3+q); at l3: 60 00 00 00, be16 =
+ *        8 + q, 3A, 40, src = D, dst = S; at l3+40: 01 04 cs cs 00 00 00 00, cs over the RFC 8200
+ *        pseudo-header (D, S, 8 + q, 58) and the message.  The reply length is R.
+ *  5. Anything else: NONE. */
+enum xsk_gpu_unreach_verdict {
+    XSK_GPU_UNREACH_NONE = 0,      /* not a UDP datagram the responder knows */
+    XSK_GPU_UNREACH_UNREACH4 = 1,  /* rewritten into ICMP port unreachable */
+    XSK_GPU_UNREACH_UNREACH6 = 2,  /* rewritten into ICMPv6 port unreachable */
+    XSK_GPU_UNREACH_MALFORMED = 3,
+    XSK_GPU_UNREACH_UNKNOWN = 4,   /* for an address the table does not hold */
+    XSK_GPU_UNREACH_UNBOUND = 5,   /* the entry's port is not bound */
+    XSK_GPU_UNREACH_LEFT = 6,      /* valid, but no error is due or the host's stack is to decide */
+    XSK_GPU_UNREACH_NO_ROOM = 7,   /* the reply does not fit the chunk */
+    XSK_GPU_UNREACH_LIMITED = 8    /* the budget was spent (xsk_gpu_unreach_serve_dev only) */
+};
+
+struct xsk_gpu_unreach_stats {   /* 64 bytes, device memory, 8-B aligned, accumulated */
+    uint64_t seen, unreach4, unreach6, reply_bytes, limited;
+    uint64_t reserved[3];        /* 0 is added */
+};
+
+struct xsk_gpu_unreach_result {  /* 32 bytes, device memory, 4-B aligned, written not accumulated */
+    uint32_t consumed;           /* c: entries taken off the ring */
+    uint32_t unreach4;
+    uint32_t unreach6;
+    uint32_t rest;               /* entries passed on, the LIMITED ones among them */
+    uint32_t backlog;            /* used(up) - c */
+    uint32_t limited;
+    uint32_t reserved[2];        /* 0 */
+};
+
+/* The rule over a device-resident list: count word, outputs (d_uverdicts, d_uports, d_reply_len),
+ * alignment rules and -EINVAL cases are those of xsk_gpu_neigh_dev(), and -EINVAL also for a
+ * chunk_size that is no power of two in [2048, 2^20] and for d_open not 4-B aligned.  No rate limit
+ * (d_ustats->limited stays).  One launch of 256-thread workgroups sized by n_max, a lane per frame for
+ * the decision, a wave per reply for the rewrite; no workspace; asynchronous and graph-capturable. */
+int xsk_gpu_unreach_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_desc* d_descs,
+                        const uint32_t* d_n, uint32_t n_max, uint32_t opts,
+                        const struct xsk_gpu_neigh_entry* d_table, uint32_t n_entries,
+                        uint32_t n_ports, const uint64_t* d_bound, const uint8_t* d_open,
+                        uint32_t chunk_size, uint8_t* d_uverdicts, uint8_t* d_uports,
+                        uint32_t* d_reply_len, struct xsk_gpu_unreach_stats* d_ustats, void* stream);
+
+/* The consumer of the `up` ring xsk_gpu_neigh_serve_dev() produces (or of the stack ring directly).
+ * The sequential rule of xsk_gpu_neigh_serve_dev() word for word, with `up` the ring consumed, `rest`
+ * the ring everything else goes to and { addr, R, 0 } the reply's descriptor, and one more step, the
+ * rate limit RFC 4443 §2.4(f) requires: *d_budget (uint32_t, 4-B aligned, read at execution; NULL:
+ * unlimited) is the number of errors this call may still send.  An entry decided UNREACH4 or UNREACH6
+ * while the budget is 0 becomes LIMITED: it is not rewritten and goes to `rest` whole; otherwise the
+ * budget falls by one when the reply is stored.  At the end *d_budget holds what is left, stored only
+ * if it moved; refilling it is the host's token bucket.  Total for any content of any index word and
+ * of the budget word.  *d_res (may be NULL) = { c, UNREACH4s, UNREACH6s, entries to rest, used(up) -
+ * c, LIMITED entries, 0, 0 }; d_ustats over the c entries.  One launch of one 1024-thread workgroup:
+ * a lane per entry decides, a wave per reply rewrites, round-robin over the 16 waves; no workspace;
+ * asynchronous and graph-capturable.
+ * -EINVAL before any device call: the rules of xsk_gpu_neigh_serve_dev() with rest in up's place and
+ * up in stack's; chunk_size as above; d_open or d_budget not 4-B aligned. */
+int xsk_gpu_unreach_serve_dev(void* d_umem, uint64_t umem_size, const struct xsk_gpu_ring_dev* up,
+                              const struct xsk_gpu_ring_dev* tx /* n_ports */, uint32_t n_ports,
+                              const struct xsk_gpu_ring_dev* rest, uint32_t max, uint32_t opts,
+                              const struct xsk_gpu_neigh_entry* d_table, uint32_t n_entries,
+                              const uint64_t* d_bound, const uint8_t* d_open, uint32_t chunk_size,
+                              uint32_t* d_budget, struct xsk_gpu_unreach_stats* d_ustats,
+                              struct xsk_gpu_unreach_result* d_res, void* stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Bench / test utilities (not on the hot path).                                               */
 /* ------------------------------------------------------------------------------------------ */
 

@@ -42,6 +42,9 @@ __all__ = [
     "neigh_table_prepare", "neigh_dev", "neigh_serve_dev",
     "ResponderQueue", "responder_queue", "responder_dev", "responder_block_size", "responder_prepare",
     "responder_queues_dev",
+    "UNREACH_STATS_DTYPE", "UNREACH_RESULT_DTYPE", "UNREACH_VERDICTS", "UNREACH_OPEN_BYTES",
+    "UNREACH_NONE", "UNREACH_UNREACH4", "UNREACH_UNREACH6", "UNREACH_MALFORMED", "UNREACH_UNKNOWN", "UNREACH_UNBOUND",
+    "UNREACH_LEFT", "UNREACH_NO_ROOM", "UNREACH_LIMITED", "unreach_dev", "unreach_serve_dev",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -95,6 +98,17 @@ NEIGH_MAX_ENTRIES = 1024  # XSK_GPU_NEIGH_MAX_ENTRIES
 # enum xsk_gpu_neigh_verdict
 NEIGH_NONE, NEIGH_ARP_REPLY, NEIGH_NA_REPLY, NEIGH_MALFORMED, NEIGH_UNKNOWN, NEIGH_UNBOUND, NEIGH_LEFT = range(7)
 NEIGH_VERDICTS = ["NONE", "ARP_REPLY", "NA_REPLY", "MALFORMED", "UNKNOWN", "UNBOUND", "LEFT"]
+# struct xsk_gpu_unreach_stats (64 B, accumulated) and struct xsk_gpu_unreach_result (32 B, written)
+UNREACH_STATS_DTYPE = np.dtype([("seen", "<u8"), ("unreach4", "<u8"), ("unreach6", "<u8"), ("reply_bytes", "<u8"),
+                                ("limited", "<u8"), ("reserved", "<u8", (3,))])
+UNREACH_RESULT_DTYPE = np.dtype([("consumed", "<u4"), ("unreach4", "<u4"), ("unreach6", "<u4"), ("rest", "<u4"),
+                                 ("backlog", "<u4"), ("limited", "<u4"), ("reserved", "<u4", (2,))])
+assert UNREACH_STATS_DTYPE.itemsize == 64 and UNREACH_RESULT_DTYPE.itemsize == 32
+# enum xsk_gpu_unreach_verdict
+(UNREACH_NONE, UNREACH_UNREACH4, UNREACH_UNREACH6, UNREACH_MALFORMED, UNREACH_UNKNOWN, UNREACH_UNBOUND, UNREACH_LEFT,
+ UNREACH_NO_ROOM, UNREACH_LIMITED) = range(9)
+UNREACH_VERDICTS = ["NONE", "UNREACH4", "UNREACH6", "MALFORMED", "UNKNOWN", "UNBOUND", "LEFT", "NO_ROOM", "LIMITED"]
+UNREACH_OPEN_BYTES = 8192  # the open-port map: a bit per UDP port
 
 
 class XskGpuError(RuntimeError):
@@ -276,6 +290,10 @@ _SIGS = {
     "xsk_gpu_responder_queues_dev": ([_P, C.c_uint32, C.c_uint32, _P], C.c_int),
     "xsk_gpu_neigh_serve_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.c_uint32, C.POINTER(RingDev),
                                  C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_unreach_dev": ([_P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32,
+                             _P, _P, _P, _P, _P], C.c_int),
+    "xsk_gpu_unreach_serve_dev": ([_P, C.c_uint64, C.POINTER(RingDev), C.POINTER(RingDev), C.c_uint32, C.POINTER(RingDev),
+                                   C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_workspace_size": ([C.c_uint32], C.c_size_t),
     "xsk_gpu_classify_dev": ([_P, C.c_uint64, _P, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
     "xsk_gpu_classify_dev_opts": ([_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_int, _P, _P, _P, _P, _P], C.c_int),
@@ -807,6 +825,33 @@ def responder_queues_dev(d_block, n_queues: int, opts: int = 0, stream=None) -> 
     block -- another count, other options, an rx_queues_prepare block -- makes the call a no-op."""
     _check("xsk_gpu_responder_queues_dev",
            lib().xsk_gpu_responder_queues_dev(_ptr(d_block), n_queues, opts, _stream_ptr(stream)))
+
+
+def unreach_dev(umem, descs, n_max: int, table, n_entries: int, n_ports: int, chunk_size: int, uverdicts, uports,
+                count=None, bound=None, open_ports=None, reply_len=None, ustats=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_unreach_dev: answer the UDP datagrams among the first min(*count, n_max) descriptors that reach an address
+    of `table` (neigh_table_prepare's, on the device) on a closed port with ICMP / ICMPv6 port unreachable, in place; the
+    reply is longer than what it quotes and must fit the frame's chunk of `chunk_size` bytes.  `open_ports`: 8192 bytes
+    on the device, a bit per listening UDP port (None: every port is closed).  uverdicts[i] is the UNREACH_* verdict,
+    uports[i] the owning port of a reply (0xFF otherwise), reply_len[i] (optional) its length; `ustats` (one
+    UNREACH_STATS_DTYPE on the device, optional) is accumulated.  No rate limit."""
+    _check("xsk_gpu_unreach_dev", lib().xsk_gpu_unreach_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), _ptr(descs), _ptr(count), n_max, opts, _ptr(table), n_entries,
+        n_ports, _ptr(bound), _ptr(open_ports), chunk_size, _ptr(uverdicts), _ptr(uports), _ptr(reply_len), _ptr(ustats),
+        _stream_ptr(stream)))
+
+
+def unreach_serve_dev(umem, up: RingDev, tx, rest: RingDev, max_entries: int, table, n_entries: int, chunk_size: int,
+                      bound=None, open_ports=None, budget=None, ustats=None, res=None, stream=None, opts: int = 0) -> None:
+    """xsk_gpu_unreach_serve_dev: the consumer of the `up` ring neigh_serve_dev produces.  Up to max_entries entries of
+    `up` are decided by unreach_dev's rule: an error is written in place and its descriptor goes onto tx[port], every
+    other entry onto `rest` as it is; the call stops in front of the first entry whose destination is full.  `budget`:
+    one uint32 word on the device, the errors the call may still send (None: unlimited); an error due behind it is
+    UNREACH_LIMITED and goes to `rest`; the word is left holding what remains.  `res`: one UNREACH_RESULT_DTYPE."""
+    _check("xsk_gpu_unreach_serve_dev", lib().xsk_gpu_unreach_serve_dev(
+        _ptr(umem), umem.numel() * umem.element_size(), C.byref(up), _ring_array(tx), len(tx), C.byref(rest),
+        max_entries, opts, _ptr(table), n_entries, _ptr(bound), _ptr(open_ports), chunk_size, _ptr(budget), _ptr(ustats),
+        _ptr(res), _stream_ptr(stream)))
 
 
 def synth_dev(umem, descs, n: int, base_off: int, stride: int, seed: int, first: int = 0, step: int = 1,
